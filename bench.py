@@ -8,12 +8,19 @@ reference's `_sba_points` run on synthetic observations - 2,000 points, 11,401
 observations, its triangulated start) on one GPU. One step = one full solve to
 convergence (the fused LM kernel reads the resident initial points and writes the
 solution to a second buffer) with every input already in HBM. `value` = frames solved
-per second over all ranks. The line also carries the metric's second half: the
-reprojection RMS of the GPU solution next to the reference's (and the oracle's).
+per second over all ranks. With `--full` the line also carries the metric's second half:
+the reprojection RMS of the GPU solution next to the reference's (and the oracle's).
 Multi-GPU (torchrun): every rank solves its own copy (weak scaling, no data-path
 collective: SBA points are independent).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
+
+A plain run does only what the headline needs: it sets up, warms up, times the K steps and
+prints the result line (metric, value, unit, ms_per_step, ...). `--dump-outputs DIR` also
+writes what the last timed step computed (DIR/points_3d.npy, the solved points a caller
+of the timed entry receives). `--full` adds everything else to the line: the convergence
+report and the reprojection RMS against the reference, the stream-launch comparison, the
+rooflines, the FTE / EKF / fused-pipeline / at-scale legs and the CPU baselines.
 """
 import argparse
 import json
@@ -35,6 +42,12 @@ def parse():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--warmup', type=int, default=20)
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed as DIR/<name>.npy')
+    ap.add_argument('--full', action='store_true',
+                    help='also run everything beside the headline: convergence report, reprojection RMS vs the '
+                         'reference, stream-launch comparison, rooflines, the FTE / EKF / pipeline / at-scale '
+                         'legs and the CPU baselines (the options below shape these)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--cpu-seconds', type=float, default=10.0)
     ap.add_argument('--fte', action='store_true', default=True, help='also time the FTE solve (configs[2])')
@@ -59,7 +72,10 @@ def parse():
     ap.add_argument('--event-every', type=int, default=8,
                     help='HIP event pairs bracket groups of this many consecutive timed steps '
                          '(kernel duration for the roofline)')
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+    return args
 
 
 def main():
@@ -114,16 +130,17 @@ def main():
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
-    # correctness + convergence of the same computation (untimed)
-    rep = ctx.sba_points_dense_dev(d_cams.data_ptr(), C, d_uv.data_ptr(), d_mask.data_ptr(), n_pts,
-                                   d_pts.data_ptr(), opts, report=True, pts_in_p=d_pts0.data_ptr())
-    sol = d_pts.cpu().numpy()
-    pos_rms = float(np.sqrt(np.mean(np.sum((sol - wl.truth) ** 2, 1))))
-    # the metric's second half (untimed): reprojection RMS of the GPU solution against the
-    # reference's own solution of the same problem (its residuals['after'])
-    res_gpu = ctx.sba_residuals(cams, wl.points_2d, wl.point_idx, wl.cam_idx, sol)
-    rms_gpu, rms_ref = workloads.reproj_rms(res_gpu), workloads.reproj_rms(wl.ref_resid_after)
-    dref = np.sqrt(np.sum((sol - wl.ref_pts) ** 2, 1))
+    if args.full:
+        # correctness + convergence of the same computation (untimed)
+        rep = ctx.sba_points_dense_dev(d_cams.data_ptr(), C, d_uv.data_ptr(), d_mask.data_ptr(), n_pts,
+                                       d_pts.data_ptr(), opts, report=True, pts_in_p=d_pts0.data_ptr())
+        sol = d_pts.cpu().numpy()
+        pos_rms = float(np.sqrt(np.mean(np.sum((sol - wl.truth) ** 2, 1))))
+        # the metric's second half (untimed): reprojection RMS of the GPU solution against the
+        # reference's own solution of the same problem (its residuals['after'])
+        res_gpu = ctx.sba_residuals(cams, wl.points_2d, wl.point_idx, wl.cam_idx, sol)
+        rms_gpu, rms_ref = workloads.reproj_rms(res_gpu), workloads.reproj_rms(wl.ref_resid_after)
+        dref = np.sqrt(np.sum((sol - wl.ref_pts) ** 2, 1))
 
     # HIP events on the kernel's stream bracket consecutive groups of `every` steps (a pair
     # per launch would cost more host time than the launch itself and add its own latency
@@ -163,10 +180,10 @@ def main():
         torch.cuda.synchronize()
 
     def timed_graph():
-        # the host bracket holds the replay and the synchronisation only; the GPU clock (for
-        # roofline.achieved) comes from a second replay bracketed by events. (Round 4 recorded
-        # the start event outside the bracket and the end event inside it: asymmetric, ADVICE
-        # r04; since round 5 neither is inside.)
+        # the host bracket holds the replay and the synchronisation only; with --full the GPU
+        # clock (for roofline.achieved) comes from a second replay bracketed by events. (Round 4
+        # recorded the start event outside the bracket and the end event inside it: asymmetric,
+        # ADVICE r04; since round 5 neither is inside.)
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
@@ -176,6 +193,8 @@ def main():
         dt = time.perf_counter() - t0
         if world > 1:
             dist.barrier()
+        if not args.full:
+            return dt, None
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(stream)
         graph.replay()
@@ -192,8 +211,13 @@ def main():
 
     dt, kern_ms = timed_graph() if graph is not None else timed_stream()
     dt = max_over_ranks(dt)
+    if args.dump_outputs and rank == 0:
+        # what the last timed step wrote: the solved points (every step solves the same resident
+        # problem, so runs with the same arguments dump the solution of identical inputs)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, 'points_3d.npy'), d_pts.cpu().numpy().astype(np.float64))
     stream_line = None
-    if graph is not None:
+    if args.full and graph is not None:
         # the same K solves launched one by one, for comparison (after the headline timing)
         dts, kms = timed_stream()
         dts = max_over_ranks(dts)
@@ -202,16 +226,6 @@ def main():
     ms_per_step = 1e3 * dt / args.steps
     frames_total = wl.n_frames * world * args.steps
     value = frames_total / dt
-
-    # roofline of the dominant kernel (k_sba_lm): algorithmic bytes per launch =
-    # frames x B_SBA, B_SBA = C*L*(2*8 + 1) + 2*3*L*8 (SURVEY.md §8(d)); the fused kernel
-    # streams the observation tensor once per solve, so this is also its HBM traffic floor.
-    L = 20
-    b_frame = C * L * 17 + 6 * L * 8
-    bytes_launch = wl.n_frames * b_frame
-    achieved = bytes_launch / (kern_ms * 1e-3) / 1e9
-    iters_mean = rep['iters_sum'] / max(1, rep['n_problems'])
-    traffic, pmc = pmc_per_launch('k_sba_lm', n_pts * _lm_group(C, n_pts))
 
     out = {
         'metric': 'frames/sec to SBA convergence, 6-cam x 20-kp (points-only SBA, configs[1])',
@@ -231,6 +245,27 @@ def main():
         'config': {'workload': f'sba_points C={C} frames={wl.n_frames}/rank L=20 (configs[1])',
                    'n_points_per_rank': int(n_pts), 'obs_slots_per_rank': int(n_pts * C),
                    'parallelism': f'frame-shard x{world}'},
+        'launch': ('one hipGraph of the K solves (K kernel nodes), replayed once in the timed region'
+                   if graph is not None else 'K stream launches'),
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    # roofline of the dominant kernel (k_sba_lm): algorithmic bytes per launch =
+    # frames x B_SBA, B_SBA = C*L*(2*8 + 1) + 2*3*L*8 (SURVEY.md §8(d)); the fused kernel
+    # streams the observation tensor once per solve, so this is also its HBM traffic floor.
+    L = 20
+    b_frame = C * L * 17 + 6 * L * 8
+    bytes_launch = wl.n_frames * b_frame
+    achieved = bytes_launch / (kern_ms * 1e-3) / 1e9
+    iters_mean = rep['iters_sum'] / max(1, rep['n_problems'])
+    traffic, pmc = pmc_per_launch('k_sba_lm', n_pts * _lm_group(C, n_pts))
+
+    out.update({
         'roofline': {'bound': 'hbm', 'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
                      'frac': achieved / HBM_PEAK_GBS, 'traffic': traffic,
                      'kernel': 'k_sba_lm', 'kernel_ms': kern_ms,
@@ -244,8 +279,6 @@ def main():
         'convergence': {'status': rep['status_counts'], 'iters_max': rep['iters_max'],
                         'gn_steps_mean': iters_mean, 'cost_before': rep['cost_before'],
                         'cost_after': rep['cost_after'], 'pos_rms_vs_truth_m': pos_rms},
-        'launch': ('one hipGraph of the K solves (K kernel nodes), replayed once in the timed region'
-                   if graph is not None else 'K stream launches'),
         'stream_launch': stream_line,
         'reproj_rms_px': rms_gpu,
         'reproj_rms_ref_px': rms_ref,
@@ -253,7 +286,7 @@ def main():
         'pos_vs_ref_m': {'rms': float(np.sqrt(np.mean(dref ** 2))), 'max': float(dref.max()),
                          'note': 'against the reference\'s scipy TRF solution of the same problem '
                                  '(it stops on xtol; SURVEY.md §8(a) a4)'},
-    }
+    })
     out['roofline_fp64'] = sba_fp64_roofline(int(mask.sum()), n_pts, iters_mean, kern_ms, pmc)
     if pmc and pmc.get('valu_insts') and pmc.get('waves'):
         # the issue rate of one wave: VALU instructions per wave (PMC) over the kernel's time

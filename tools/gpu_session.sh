@@ -25,12 +25,12 @@ if [[ $STEPS == *all* || $STEPS == *smoke* ]]; then
   run smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
 fi
 if [[ $STEPS == *all* || $STEPS == *bench* ]]; then
-  run bench 600 python bench.py ${BENCH_ARGS:-}
+  run bench 600 python bench.py --full ${BENCH_ARGS:-}
   grep '^{' "$OUT/bench.log" > "$OUT/bench_${TAG}.json" || true
 fi
 if [[ $STEPS == *all* || $STEPS == *prof* ]]; then
   export TMPDIR=/tmp
-  run rocprof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_${TAG}" -o run -- python3 "$REPO/bench.py" --no-cpu-baseline --steps 200 --warmup 20 ${BENCH_ARGS:-}
+  run rocprof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_${TAG}" -o run -- python3 "$REPO/bench.py" --full --no-cpu-baseline --steps 200 --warmup 20 ${BENCH_ARGS:-}
 fi
 if [[ $STEPS == *ftetrace* ]]; then
   export TMPDIR=/tmp
@@ -44,7 +44,7 @@ fi
 if [[ ",$STEPS," == *,pmc,* ]]; then
   # HBM traffic (guide: separate passes; FETCH_SIZE x2 on gfx950) and FP64 VALU counts
   export TMPDIR=/tmp
-  PMC_ARGS="--no-cpu-baseline --no-fte --steps 3 --warmup 1 --ekf-seqs 0 --pipeline-seqs 0 --window-frames 0"
+  PMC_ARGS="--full --no-cpu-baseline --no-fte --steps 3 --warmup 1 --ekf-seqs 0 --pipeline-seqs 0 --window-frames 0"
   PMC_VALU=${PMC_VALU:-"SQ_INSTS_VALU SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_TRANS_F64 SQ_WAVES SQ_INSTS_SALU SQ_WAVE_CYCLES"}
   run pmc_fetch 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_${TAG}_fetch" -o run -- python3 "$REPO/bench.py" $PMC_ARGS
   run pmc_write 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_${TAG}_write" -o run -- python3 "$REPO/bench.py" $PMC_ARGS
