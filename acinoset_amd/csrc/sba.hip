@@ -33,7 +33,7 @@ struct SbaParams {
 };
 
 // HOIST: each lane keeps its camera record in registers for the whole LM loop instead of
-// re-reading it from LDS in every projection (198 VGPRs: 2 waves per SIMD), chosen for
+// re-reading it from LDS in every projection (196 VGPRs: 2 waves per SIMD), chosen for
 // grids of at most 2 waves per SIMD, where nothing else would fill the SIMD anyway.
 // The other instances are not occupancy-bound either: <4, 3> (the configs[4] shape) holds 186
 // VGPRs, 2 waves per SIMD, and register budgets for 2 / 3 / 4 waves per SIMD
@@ -108,30 +108,45 @@ __global__ __launch_bounds__(256) void k_sba_lm(const double* __restrict__ cams,
     ou[s] = ok[s] ? q[s].x : 0.0;
     ov[s] = ok[s] ? q[s].y : 0.0;
     oc[s] = s_cam + (ok[s] ? cam : C) * ACS_CAM_STRIDE;
-    if constexpr (HOIST) {
-#pragma unroll
-      for (int i = 0; i < ACS_CAM_STRIDE; ++i) cr[s][i] = ok[s] ? cr[s][i] : (i == 19 ? 1.0 : 0.0);
-    }
     mine += ok[s] ? 1 : 0;
   }
-  const double nobs = group_sum<G>((double)mine);
-  if (nobs == 0.0) {
-    if (lane == 0) {
-      pts[3 * p] = x0;
-      pts[3 * p + 1] = x1;
-      pts[3 * p + 2] = x2;
-      if (stat) {
-        cost0[p] = 0.0;
-        cost1[p] = 0.0;
-        stat[3 * p] = ACS_STATUS_NOOBS;
-        stat[3 * p + 1] = 0;
-        stat[3 * p + 2] = 0;
-      }
-    }
-    return;
-  }
+  // a point without any observation: no lane of its group has one (the lanes of a dead
+  // group have left, and a ballot counts them as zero). It takes no path of its own ahead of
+  // the loop, where the branch would stand between the loads and everything that can run
+  // under their latency: all its slots are the null camera, its sums are exact zeros, a
+  // max_iters of 0 ends it at the first exit of the first pass with its point untouched, and
+  // its report is set right after the loop.
+  const unsigned long long has = __ballot(mine > 0);
+  const unsigned long long grp = G == 64 ? ~0ull : (1ull << (G & 63)) - 1ull;
+  const bool noobs = ((has >> (threadIdx.x & 63 & ~(G - 1))) & grp) == 0ull;
+  const int max_iters = noobs ? 0 : prm.max_iters;
   const double f2 = prm.f_scale * prm.f_scale;
   const double if2 = 1.0 / f2;
+  if constexpr (HOIST) {
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+      // the null record over the loaded one: 20 64-bit moves under one saved exec mask, in
+      // place of 40 32-bit selects and the moves that hold their constants. One asm statement
+      // and no branch, so that the scheduler still places it, and the wait for the record's
+      // loads that it needs, behind the constant set-up that runs under the load latency.
+      static_assert(ACS_CAM_STRIDE == 20, "the null-record moves below are written out for 20 doubles");
+      const unsigned long long nul = __ballot(!ok[s]);
+      unsigned long long sv;
+      double* c = cr[s];
+      asm("s_and_saveexec_b64 %[sv], %[nul]\n\t"
+          "v_mov_b64 %0, 0\n\tv_mov_b64 %1, 0\n\tv_mov_b64 %2, 0\n\tv_mov_b64 %3, 0\n\t"
+          "v_mov_b64 %4, 0\n\tv_mov_b64 %5, 0\n\tv_mov_b64 %6, 0\n\tv_mov_b64 %7, 0\n\t"
+          "v_mov_b64 %8, 0\n\tv_mov_b64 %9, 0\n\tv_mov_b64 %10, 0\n\tv_mov_b64 %11, 0\n\t"
+          "v_mov_b64 %12, 0\n\tv_mov_b64 %13, 0\n\tv_mov_b64 %14, 0\n\tv_mov_b64 %15, 0\n\t"
+          "v_mov_b64 %16, 0\n\tv_mov_b64 %17, 0\n\tv_mov_b64 %18, 0\n\tv_mov_b64 %19, 1.0\n\t"
+          "s_mov_b64 exec, %[sv]"
+          : "+v"(c[0]), "+v"(c[1]), "+v"(c[2]), "+v"(c[3]), "+v"(c[4]), "+v"(c[5]), "+v"(c[6]), "+v"(c[7]),
+            "+v"(c[8]), "+v"(c[9]), "+v"(c[10]), "+v"(c[11]), "+v"(c[12]), "+v"(c[13]), "+v"(c[14]), "+v"(c[15]),
+            "+v"(c[16]), "+v"(c[17]), "+v"(c[18]), "+v"(c[19]), [sv] "=&s"(sv)
+          : [nul] "s"(nul)
+          : "scc");
+    }
+  }
 
   // One pass over the observations at X: robust cost, Triggs-weighted GN matrix (packed
   // upper 3x3) and IRLS gradient, group-reduced. The trial point of every LM iteration is
@@ -197,91 +212,85 @@ __global__ __launch_bounds__(256) void k_sba_lm(const double* __restrict__ cams,
   const double F_before = F;
   double lam = 1e-3;
   int status = ACS_STATUS_RUNNING, iters = 0, nfev = 1;
-  while (status == ACS_STATUS_RUNNING) {
-    if (iters >= prm.max_iters) {
-      status = ACS_STATUS_MAXITER;
-      break;
-    }
+  // One pass = solve, stopping tests on the solve, trial linearisation, accept / reject. The
+  // pass is straight-line code with two exits (after the solve; at the end): a lone wave pays
+  // an issue slot for every exec-mask instruction and branch, so a pass that cannot step (not
+  // positive definite) is a predicate on the same code, not a path of its own.
+  while (true) {
     const double gmax = fmax(fabs(g[0]), fmax(fabs(g[1]), fabs(g[2])));
-    if (gmax <= prm.gtol) {
-      status = ACS_STATUS_GTOL;
-      break;
-    }
     // Cholesky of H + lam*diag(H)
     const double dl = 1.0 + lam;
     const double a00 = H[0] * dl, a11 = H[3] * dl, a22 = H[5] * dl;
-    bool pd = a00 > 0.0;
-    // reciprocal Cholesky diagonal; the argument, not the result, is selected (rsq_nr(1) = 1):
-    // no branch around the reciprocal square roots
-    const double i00 = rsq_nr(pd ? a00 : 1.0);
+    // reciprocal Cholesky diagonal, unguarded: a pivot that is not positive makes its
+    // reciprocal square root, and all that follows from it, infinite or NaN garbage, and
+    // clears pd, the predicate on every use of the step below (uniform over the group: it
+    // comes from the group-summed H)
+    const double i00 = rsq_nr(a00);
     const double L10 = H[1] * i00, L20 = H[2] * i00;
     const double d11 = a11 - L10 * L10;
-    pd = pd && d11 > 0.0;
-    const double i11 = rsq_nr(pd ? d11 : 1.0);
+    const double i11 = rsq_nr(d11);
     const double L21 = (H[4] - L20 * L10) * i11;
     const double d22 = a22 - L20 * L20 - L21 * L21;
-    pd = pd && d22 > 0.0;
-    const double i22 = rsq_nr(pd ? d22 : 1.0);
-    double dx0 = 0.0, dx1 = 0.0, dx2 = 0.0;
-    if (pd) {
-      const double y0 = -g[0] * i00;
-      const double y1 = (-g[1] - L10 * y0) * i11;
-      const double y2 = (-g[2] - L20 * y0 - L21 * y1) * i22;
-      dx2 = y2 * i22;
-      dx1 = (y1 - L21 * dx2) * i11;
-      dx0 = (y0 - L10 * dx1 - L20 * dx2) * i00;
-      // model decrease of the step, -g.dx - dx.H.dx/2: below the resolution of the
-      // float64 cost the step can only be accepted or rejected by rounding -> converged
-      const double Hd0 = H[0] * dx0 + H[1] * dx1 + H[2] * dx2;
-      const double Hd1 = H[1] * dx0 + H[3] * dx1 + H[4] * dx2;
-      const double Hd2 = H[2] * dx0 + H[4] * dx1 + H[5] * dx2;
-      const double pred = -(g[0] * dx0 + g[1] * dx1 + g[2] * dx2) - 0.5 * (dx0 * Hd0 + dx1 * Hd1 + dx2 * Hd2);
-      if (pred <= ACS_COST_RES * F) {
-        status = ACS_STATUS_FTOL;
-        break;
-      }
-    }
+    const double i22 = rsq_nr(d22);
+    const bool pd = a00 > 0.0 && d11 > 0.0 && d22 > 0.0;
+    const double y0 = -g[0] * i00;
+    const double y1 = (-g[1] - L10 * y0) * i11;
+    const double y2 = (-g[2] - L20 * y0 - L21 * y1) * i22;
+    double dx2 = y2 * i22;
+    double dx1 = (y1 - L21 * dx2) * i11;
+    double dx0 = (y0 - L10 * dx1 - L20 * dx2) * i00;
+    // the step's products are rounded before anything is added to them (x + dx below is an
+    // addition of the rounded step, never a multiply-add fused with the last product above)
+    asm volatile("" : "+v"(dx0), "+v"(dx1), "+v"(dx2));
+    // model decrease of the step, -g.dx - dx.H.dx/2: below the resolution of the
+    // float64 cost the step can only be accepted or rejected by rounding -> converged
+    const double Hd0 = H[0] * dx0 + H[1] * dx1 + H[2] * dx2;
+    const double Hd1 = H[1] * dx0 + H[3] * dx1 + H[4] * dx2;
+    const double Hd2 = H[2] * dx0 + H[4] * dx1 + H[5] * dx2;
+    const double pred = -(g[0] * dx0 + g[1] * dx1 + g[2] * dx2) - 0.5 * (dx0 * Hd0 + dx1 * Hd1 + dx2 * Hd2);
+    // first exit: max_iters, gtol or the cost resolution; which of them is sorted out after
+    // the loop (status is still RUNNING here), not with three selects in every pass
+    if ((iters >= max_iters) | (gmax <= prm.gtol) | (pd & (pred <= ACS_COST_RES * F))) break;
     ++iters;
-    if (!pd) {
-      // not positive definite (lam near its floor on a degenerate point): no step, so no
-      // trial and no xtol test; raise lam as a rejection would (uniform over the group:
-      // pd comes from the group-summed H)
-      lam *= 10.0;
-      if (lam > 1e16) status = ACS_STATUS_STALLED;
-      continue;
-    }
     const double n0 = x0 + dx0, n1 = x1 + dx1, n2 = x2 + dx2;
     double Hn[6], gn[3], Fn;
     linearize(n0, n1, n2, Hn, gn, Fn);
-    ++nfev;
+    // not positive definite: no step, so the trial does not count, there is no xtol test, and
+    // lam rises as for a rejection
+    nfev += pd ? 1 : 0;
     // |dx| <= xtol (xtol + |x|), compared squared
     const double xx = x0 * x0 + x1 * x1 + x2 * x2;
-    const double xn = xx > 0.0 ? xx * rsq_nr(xx > 0.0 ? xx : 1.0) : 0.0;
+    // |x| = xx / sqrt(xx) without a branch or select for xx = 0: the smallest normal number
+    // stands in for it, and 0 times its finite reciprocal root is exactly 0 (an xx below it
+    // is an |x| below 1.5e-154, which xtol + |x| rounds away either way)
+    const double xn = xx * rsq_nr(fmax(xx, 2.2250738585072014e-308));
     const double xb = prm.xtol * (prm.xtol + xn);
-    const bool small = dx0 * dx0 + dx1 * dx1 + dx2 * dx2 <= xb * xb;
-    if (Fn < F) {
-      const bool fconv = (F - Fn) <= prm.ftol * F;
+    const bool small = pd && dx0 * dx0 + dx1 * dx1 + dx2 * dx2 <= xb * xb;
+    const bool acc = pd && Fn < F;
+    const bool fconv = acc && (F - Fn) <= prm.ftol * F;
+    lam = acc ? fmax(lam * 0.1, 1e-15) : lam * 10.0;
+    if (acc) {
       x0 = n0;
       x1 = n1;
       x2 = n2;
-      lam = fmax(lam * 0.1, 1e-15);
       F = Fn;
 #pragma unroll
       for (int i = 0; i < 6; ++i) H[i] = Hn[i];
       g[0] = gn[0];
       g[1] = gn[1];
       g[2] = gn[2];
-      if (fconv)
-        status = ACS_STATUS_FTOL;
-      else if (small)
-        status = ACS_STATUS_XTOL;
-    } else {
-      lam *= 10.0;
-      if (small)
-        status = ACS_STATUS_XTOL;
-      else if (lam > 1e16)
-        status = ACS_STATUS_STALLED;
     }
+    // second exit, rising priority: stalled (lam only passes 1e16 on a pass without an
+    // accepted step), xtol, ftol of an accepted step
+    status = lam > 1e16 ? ACS_STATUS_STALLED : ACS_STATUS_RUNNING;
+    status = small ? ACS_STATUS_XTOL : status;
+    status = fconv ? ACS_STATUS_FTOL : status;
+    if (status != ACS_STATUS_RUNNING) break;
+  }
+  if (status == ACS_STATUS_RUNNING) {
+    // left at the first exit (g is the one tested there), in the order of its tests
+    const double gmax = fmax(fabs(g[0]), fmax(fabs(g[1]), fabs(g[2])));
+    status = iters >= max_iters ? ACS_STATUS_MAXITER : gmax <= prm.gtol ? ACS_STATUS_GTOL : ACS_STATUS_FTOL;
   }
   if (lane == 0) {
     pts[3 * p] = x0;
@@ -290,11 +299,11 @@ __global__ __launch_bounds__(256) void k_sba_lm(const double* __restrict__ cams,
     // the per-point costs and status feed k_sba_report only: not written (28 B per point)
     // when no report is asked for
     if (stat) {
-      cost0[p] = F_before;
-      cost1[p] = F;
-      stat[3 * p] = status;
+      cost0[p] = noobs ? 0.0 : F_before;
+      cost1[p] = noobs ? 0.0 : F;
+      stat[3 * p] = noobs ? ACS_STATUS_NOOBS : status;
       stat[3 * p + 1] = iters;
-      stat[3 * p + 2] = nfev;
+      stat[3 * p + 2] = noobs ? 0 : nfev;
     }
   }
 }

@@ -1,6 +1,6 @@
 """Bitwise A/B of two builds of the SBA kernel: run the headline problem and the configs[4]-shape one
-with the library named by
-ACINOSET_HIP_LIB; save the solutions and per-point status for a bitwise comparison."""
+with the library named by ACINOSET_HIP_LIB (tag 'head' first, then tag 'new'); save the solutions and the
+report (status counts, iteration and evaluation sums, cost sums) for a bitwise comparison."""
 import os, sys, time
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 import numpy as np
@@ -25,6 +25,10 @@ for name, cams, uv, mask, pts0 in probs:
     rep = ctx.sba_points_dense_dev(d_cams.data_ptr(), C, d_uv.data_ptr(), d_mask.data_ptr(), n_pts, d_pts.data_ptr(),
                                    opts, report=True, pts_in_p=d_pts0.data_ptr())
     out[name] = d_pts.cpu().numpy()
+    # the report reduces the per-point status, iteration and evaluation counts and costs in a fixed order
+    out[name + '_counts'] = np.array([rep['status_counts'][k] for k in sorted(rep['status_counts'])]
+                                     + [rep['iters_max'], rep['iters_sum'], rep['nfev_sum']], np.int64)
+    out[name + '_costs'] = np.array([rep['cost_before'], rep['cost_after']])
     torch.cuda.synchronize()
     ts = []
     for r in range(3):
@@ -41,4 +45,4 @@ if tag == 'new' and os.path.exists('gpurun_out/sba_bits_head.npz'):
     h = np.load('gpurun_out/sba_bits_head.npz')
     for k in out:
         print(k, 'bit-identical' if np.array_equal(h[k].view(np.uint64), out[k].view(np.uint64)) else
-              f'DIFFER max {np.abs(h[k] - out[k]).max():.3e}')
+              f'DIFFER max {np.abs(h[k] - out[k]).max():.3e}', flush=True)
