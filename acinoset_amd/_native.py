@@ -39,7 +39,7 @@ SYMBOLS = (
     'acs_fte_dist_create', 'acs_fte_dist_init', 'acs_fte_dist_round', 'acs_fte_dist_poll',
     'acs_fte_dist_gather', 'acs_fte_dist_scatter', 'acs_fte_dist_result',
     'acs_fte_dist_destroy', 'acs_fte_dist_reset', 'acs_alloc_events', 'acs_ekf_singular_count',
-    'acs_fte_debug_blocks',
+    'acs_fte_debug_blocks', 'acs_fte_debug_plan',
     'acs_sba_ext_dist_create', 'acs_sba_ext_dist_init', 'acs_sba_ext_dist_round', 'acs_sba_ext_dist_poll',
     'acs_sba_ext_dist_result', 'acs_sba_ext_dist_destroy', 'acs_ekf_run',
     'acs_sba_ekf_pipeline',
@@ -164,6 +164,7 @@ def _declare(lib):
                                    _P, _P, _P, u32]),
         'acs_fte_debug_blocks': (C.c_int, [_P, _P, i64, _P, i64, _P, i32, _P, _P, i32, i32, dbl, _P, i32, i32, _P, _P,
                                            dbl, i32, _P, C.POINTER(i64), u32]),
+        'acs_fte_debug_plan': (C.c_int, [_P, i32, i32, i32, i32, i32, i32, C.POINTER(i32), C.POINTER(i32), i32]),
         'acs_triangulate_pairs': (C.c_int, [_P, _P, i32, _P, _P, _P, _P, i64, _P, u32]),
         'acs_triangulate_dense': (C.c_int, [_P, _P, i32, _P, _P, i64, _P, _P, u32]),
         'acs_sba_ext_default_opts': (None, [C.POINTER(SbaExtOpts)]),
@@ -200,6 +201,28 @@ def _declare(lib):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
+
+
+def fte_debug_plan(n_frames, P, n_cams, shutter_delay=True, sd_mode='const', n_cu=None, ctx=None):
+    """acs_fte_debug_plan (test hook, no GPU needed with n_cu): the kernels and grids acs_fte_solve
+    picks for this problem size on a device of n_cu CUs (None: the device of `ctx`). Returns a dict:
+    nblk, nlev, BP, GR, Cg, asm (512 / 1024 threads of k_cr_assemble_build, 0: k_cr_build), lin
+    (k_fte_linearize instance), d_upper, and levels = [(ne, ns, nsplit, deep)] per reduction level."""
+    if n_cu is None and ctx is None:
+        raise ValueError('fte_debug_plan: give n_cu or ctx')
+    lib = load_library()
+    head = (C.c_int32 * 8)()
+    lv = (C.c_int32 * (4 * 32))()
+    rc = lib.acs_fte_debug_plan(ctx.h if n_cu is None else None, 0 if n_cu is None else int(n_cu), int(n_frames),
+                                int(P), int(n_cams), int(bool(shutter_delay)), int(SD_MODES.get(sd_mode, sd_mode)),
+                                head, lv, 32)
+    if rc != 0:
+        raise ValueError(f'acs_fte_debug_plan: bad arguments (rc {rc})')
+    keys = ('nblk', 'nlev', 'BP', 'GR', 'Cg', 'asm', 'lin', 'd_upper')
+    plan = {k: int(head[i]) for i, k in enumerate(keys)}
+    plan['levels'] = [(int(lv[4 * l]), int(lv[4 * l + 1]), int(lv[4 * l + 2]), bool(lv[4 * l + 3]))
+                      for l in range(plan['nlev'])]
+    return plan
 
 
 def alloc_events():

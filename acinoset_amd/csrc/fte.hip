@@ -742,6 +742,10 @@ struct RowCmp {
     return -1;
   }
 };
+// threads that assemble one row: a third of k_cr_assemble_build's block in whole half-waves (the
+// 512-thread compact form, the 1,024-thread form), k_fte_assemble's whole block
+constexpr int asm_row_threads(int TH) { return TH / 3 / 32 * 32; }
+constexpr int ASM_GT_CMP = asm_row_threads(512), ASM_GT_FULL = asm_row_threads(1024), ASM_TH_ROWS = 256;
 template <bool CMP>
 __device__ void assemble_row(const FteDims& d, int f, const double* __restrict__ X, const double* __restrict__ qinv,
                              int lo, int hi, const double* __restrict__ Hloc, const double* __restrict__ gloc,
@@ -773,6 +777,8 @@ __device__ void assemble_row(const FteDims& d, int f, const double* __restrict__
     // wave holds two of these load branches (the compiler waited for a branch's loads before the
     // next branch's, a round trip per branch of one wave).
     constexpr int S0 = 64;
+    static_assert(FK_MAXP <= S0, "the gradient specials t < P are the first wave of the row's group");
+    static_assert(S0 + 12 + 3 * FTE_MAXC <= ASM_GT_CMP, "second-round threads within a 512-thread row group");
     const int nS1 = 12 + 3 * Cg;  // nth >= S0 + nS1 (<= 124: 16 delays)
     if (t < P) {
       // every load unconditional (valid clamped addresses), the terms that do not apply selected
@@ -833,6 +839,8 @@ __device__ void assemble_row(const FteDims& d, int f, const double* __restrict__
     // the 1,024-thread rows (and k_fte_assemble) keep the branch per special kind: the
     // regrouped form above costs them 6 spilled VGPRs within 64, and 17.3 -> 17.9 us at 1,000
     // frames (profiles/r06/fte_kernel_totals_*_r06ze.log)
+    static_assert(FK_MAXP + 12 + 3 * FTE_MAXC <= ASM_GT_FULL && FK_MAXP + 12 + 3 * FTE_MAXC <= ASM_TH_ROWS,
+                  "second-round threads within a 1,024-thread row group and k_fte_assemble's block");
     const int nOff = P + 12, nS = nOff + 3 * Cg;
     if (t < P) {
       sg[0] = oo ? gloc[(size_t)kown * FTE_NZP + t] : 0.0;
@@ -993,6 +1001,7 @@ __global__ __launch_bounds__(256) void k_fte_assemble(FteDims d, const double* _
                                                       double* __restrict__ gmaxp, double* __restrict__ Adiag,
                                                       int hsel, double* __restrict__ graw = nullptr,
                                                       double* __restrict__ gmaxt = nullptr) {
+  static_assert(ASM_TH_ROWS == 256, "assemble_row's bound for this kernel's block");
   // Terms are owned by the lowest X row they touch: frame k (rows k..k+2) iff lo <= k < hi,
   // model stencil m (rows m-3..m) iff lo <= m-3 < hi. The single-GPU solve owns all terms;
   // a frame-window rank owns the terms starting in its window (dist path below).
@@ -1290,7 +1299,7 @@ __global__ __launch_bounds__(TH) __attribute__((amdgpu_waves_per_eu(8))) void k_
     s_p[r] = r - (r / P) * P;
   }
   {
-    constexpr int GT = TH / 3 / 32 * 32;  // threads per row (320, 160)
+    constexpr int GT = asm_row_threads(TH);  // threads per row (320, 160)
     const int grp = tid / GT, a = grp < 3 ? grp : 0;
     const int f = 3 * i + a;
     const bool act = grp < 3 && f < d.M;
@@ -1498,6 +1507,13 @@ __device__ __forceinline__ void cr_top_border_sums(const FteDims& d, const FteSt
 // column-block of GB (GR = 16: up to 15 cameras with a constant shutter delay); otherwise
 // E_r is read from global memory (k_cr_level's sEr == nullptr path)
 __host__ __device__ __forceinline__ bool cr_er_lds(int NB, int GR) { return NB <= 5 && GR <= 16; }
+// k_cr_level's deep path (full tiles; few column-blocks per workgroup, whose W column-blocks
+// fit the two pivot buffers): the kernel's branch and the host's bookkeeping of which levels
+// stored upper tiles (cr_launch_level) are this one test
+__host__ __device__ __forceinline__ bool cr_level_deep(int BP, int NBB, int nsplit) {
+  const int BUF = 16 * 17 + 16 * BP + BP * 17;
+  return nsplit >= 3 && ((NBB + nsplit - 1) / nsplit) * BP * 16 <= 2 * BUF;
+}
 __host__ __device__ __forceinline__ size_t cr_level_lds_doubles(int BP, int GR) {
   return 2 * (16 * 17 + 16 * (size_t)BP + 17 * (size_t)BP) + (size_t)BP * GR +
          (cr_er_lds(BP >> 4, GR) ? 2 * (size_t)BP + 1 : (size_t)BP) * BP;
@@ -1931,7 +1947,7 @@ __global__ __launch_bounds__(1024) void k_cr_level(FteDims d, int s, int a0, int
   PROFA(29, 15);
   PROFA(31, 0);
   PROF(1);
-  if (nsplit >= 3 && ((NBB + nsplit - 1) / nsplit) * BP * 16 <= 2 * BUF) {
+  if (cr_level_deep(BP, NBB, nsplit)) {
     // Deep levels (few column-blocks per workgroup): the Schur terms are dealt out to all 16
     // waves instead of each column wave forming its own 2 NB output tiles, which would
     // serialise on one SIMD's matrix core. The W column-blocks go to LDS (the pivot buffers
@@ -2968,9 +2984,30 @@ static void fte_launch_lin(const FteDims& d, hipStream_t s, const FteBuffers& b,
 
 struct FteSetup {
   FteState* snap = nullptr;  // pinned host slots the LM kernel writes its state into
+  int n_cu = 256;            // the context's device (k_cr_assemble_build's instance: cr_asm_threads)
   FteDims d;
   FteBuffers b;
 };
+
+// The sizes that choose the solve's kernels and grids: the 3-frame super-blocks (nblk of BP
+// rows), the tau border (Cg constant delays + the gradient column, GR wide) and the
+// cyclic-reduction depth
+static void fte_shape(FteDims& d, int N, int P, int n_cams, int sd, int sd_mode) {
+  d.N = N;
+  d.M = N + 2;
+  d.P = P;
+  d.C = n_cams;
+  d.var = sd && sd_mode == 1;
+  d.Ct = sd ? n_cams : 0;
+  d.Cg = sd && !d.var ? n_cams : 0;
+  d.NT = d.var ? N * n_cams : n_cams;
+  d.NZ = P + 6 + d.Ct;
+  d.nblk = (d.M + 2) / 3;
+  d.BP = ((3 * P + 15) / 16) * 16;
+  d.GR = ((d.Cg + 1 + 15) / 16) * 16;
+  d.nlev = 0;
+  for (int s = 1; s < d.nblk; s <<= 1) d.nlev++;
+}
 
 // Dimensions, device buffers and initial state of one FTE problem. With `owned` == NULL
 // the buffers live in the context workspace (acs_fte_solve / acs_fte_eval); otherwise one
@@ -2995,32 +3032,20 @@ static int fte_setup(acs_ctx* ctx, FteSetup& S, const int32_t* skel_ints, int64_
             "fte: shutter_delay=%d needs intermode %s (got %d), as src/core/fte.py:44-48", sd,
             sd ? "vel/acc" : "pos", intermode);
   ACS_CHECK(ctx, sd_mode == 0 || sd_mode == 1, "fte: shutter_delay_mode %d (0 const, 1 variable)", sd_mode);
+  S.n_cu = ctx->n_cu;
   FteDims& d = S.d;
-  d.N = N;
-  d.M = N + 2;
-  d.P = P;
+  fte_shape(d, N, P, n_cams, sd, sd_mode);
   d.L = L;
-  d.C = n_cams;
-  d.var = sd && sd_mode == 1;
-  d.Ct = sd ? n_cams : 0;
-  d.Cg = sd && !d.var ? n_cams : 0;
-  d.NT = d.var ? N * n_cams : n_cams;
   d.nint = (int)n_ints;
   d.nreal = (int)n_reals;
   d.pad_ = 0;
-  d.NZ = P + 6 + d.Ct;
   ACS_CHECK(ctx, d.NZ <= FTE_NZP, "fte: P + 6 + C = %d exceeds %d", d.NZ, FTE_NZP);
   d.im = intermode;
   d.Ts = Ts;
   d.la = la;
   d.lb = lb;
   d.lc = lc;
-  d.nblk = (d.M + 2) / 3;
-  d.BP = ((3 * P + 15) / 16) * 16;
   ACS_CHECK(ctx, d.BP <= CR_MAXBP, "fte: 3P = %d exceeds %d", 3 * P, CR_MAXBP);
-  d.GR = ((d.Cg + 1 + 15) / 16) * 16;
-  d.nlev = 0;
-  for (int s = 1; s < d.nblk; s <<= 1) d.nlev++;
   const int M = d.M, C = d.C, BP = d.BP, GR = d.GR, n = d.nblk;
   FteBuffers& b = S.b;
   size_t off = 0;
@@ -3199,10 +3224,7 @@ static int cr_launch_level(const FteDims& d, hipStream_t s, int sl, int a0, int 
   }
 #undef CR_LEVEL
 #undef CR_LEVEL_
-  // the kernel's deep-path test (full tiles)
-  const int BPq = d.BP, BUF = 16 * 17 + 16 * BPq + BPq * 17;
-  const bool deep = nsplit >= 3 && ((NBB + nsplit - 1) / nsplit) * BPq * 16 <= 2 * BUF;
-  return (ne > 0 && !deep) ? 1 : 0;
+  return (ne > 0 && !cr_level_deep(d.BP, NBB, nsplit)) ? 1 : 0;
 }
 
 static bool cr_defer() {
@@ -3224,6 +3246,15 @@ static bool fte_d_upper(const FteDims& d) {
   return !d.var && d.GR <= 16 && !cr_defer() && !full;
 }
 
+// blocks eliminated (ne) and survivors applying the previous level's terms (ns) at the level of
+// step sl of the chain [a0, top]
+static void cr_level_counts(int a0, int iend, int top, int sl, int* ne, int* ns) {
+  *ne = *ns = 0;
+  for (int i = a0 + sl; i < iend; i += 2 * sl) ++*ne;
+  if (sl > 1)
+    for (int j = a0; j <= top; j += 2 * sl) ++*ns;
+}
+
 // Block cyclic reduction of super-blocks [a0, top] (blocks < iend may be eliminated; a
 // chain end at iend survives), nlev levels, then (final_apply) every pending Schur term is
 // applied to the survivors. Survivor workgroups apply the previous level's terms at every
@@ -3242,10 +3273,8 @@ static const double* cr_reduce(const FteDims& d, hipStream_t s, const FteState* 
   CrPending pend;
   int sl = 1;
   for (int lv = 0; lv < nlev; ++lv, sl <<= 1) {
-    int ne = 0, ns = 0;
-    for (int i = a0 + sl; i < iend; i += 2 * sl) ++ne;
-    if (sl > 1)
-      for (int j = a0; j <= top; j += 2 * sl) ++ns;
+    int ne, ns;
+    cr_level_counts(a0, iend, top, sl, &ne, &ns);
     if (ns && defer && ne * cr_nsplit(d, ne, ns) + ns > 256) ns = 0;  // defer
     // level 0 of a chain built by k_cr_assemble_build / k_cr_build: every E is upper triangular.
     // d_upper (D stored as upper tiles): levels 0 and 1 read D as assembled (the level-1
@@ -3302,17 +3331,16 @@ static void cr_launch_top(const FteDims& d, hipStream_t s, int nlev, int a0, int
 #undef CR_TOP_
 }
 
-static void cr_launch_assemble_build(const FteDims& d, hipStream_t s, const FteBuffers& b, int b0 = 0,
+// threads per block of k_cr_assemble_build: the 512-thread instance (compact LDS rows) when the
+// grid is more than one round of 1024-thread blocks, two per CU
+static int cr_asm_threads(int nblk, int n_cu) { return nblk > 2 * n_cu ? 512 : 1024; }
+
+static void cr_launch_assemble_build(const FteDims& d, int n_cu, hipStream_t s, const FteBuffers& b, int b0 = 0,
                                      int nblk = -1, int lo = 0, int hi = INT_MAX, int end_l = -1, int end_r = -1,
                                      double* rdiag = nullptr, double* graw = nullptr, int d_full = 0) {
   if (nblk < 0) nblk = d.nblk;
   if (nblk <= 0) return;
-  static const int n_cu = [] {
-    int dev = 0, n = 0;
-    (void)hipGetDevice(&dev);
-    return hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0 ? n : 256;
-  }();
-  const bool wide = nblk > 2 * n_cu;  // more than one round of 1024-thread blocks
+  const bool wide = cr_asm_threads(nblk, n_cu) < 1024;
 #define CR_ABUILD_(nb, th)                                                                                  \
   hipLaunchKernelGGL((k_cr_assemble_build<nb, th>), dim3(nblk), dim3(th), asm_build_lds_bytes(d, th < 1024), s, d, b.X, \
                      b.qinv, b.st, b.Hloc, b.gloc, b.Dc, b.Ec, b.GBc, b.gmaxp, b0, lo, hi, end_l, end_r, rdiag, graw, \
@@ -3355,7 +3383,8 @@ static void fte_enqueue_iteration(FteSetup& S, hipStream_t s, const FteOptsDev& 
                        b.Hloc, b.gloc, b.Ab, b.gb, b.Bt, b.gmaxp, b.Adiag, 1);
     cr_launch_build(d, s, d.nblk, b.st, b.Ab, b.gb, b.Bt, b.Dc, b.Ec, b.GBc, 0, -1, -1, b.Adiag);
   } else {
-    cr_launch_assemble_build(d, s, b, 0, -1, 0, INT_MAX, -1, -1, nullptr, nullptr, fte_d_upper(d) ? 0 : 1);
+    cr_launch_assemble_build(d, S.n_cu, s, b, 0, -1, 0, INT_MAX, -1, -1, nullptr, nullptr,
+                             fte_d_upper(d) ? 0 : 1);
   }
   const int bend = d.nblk - 1;
   CrPending pend;
@@ -4035,7 +4064,8 @@ int acs_fte_debug_blocks(acs_ctx* ctx, const int32_t* skel_ints, int64_t n_ints,
   fte_launch_lin(d, s, b, 1, 0, d.N, 0, (double*)nullptr, (const double*)nullptr);
   const int L = std::min((int)levels, d.nlev);
   // as the solve stores it (upper tiles) unless the assembled D itself is asked for
-  cr_launch_assemble_build(d, s, b, 0, -1, 0, INT_MAX, -1, -1, nullptr, nullptr, L == 0 || !fte_d_upper(d) ? 1 : 0);
+  cr_launch_assemble_build(d, S.n_cu, s, b, 0, -1, 0, INT_MAX, -1, -1, nullptr, nullptr,
+                           L == 0 || !fte_d_upper(d) ? 1 : 0);
   if (L > 0) cr_reduce(d, s, b.st, b, 0, d.nblk, d.nblk - 1, L, b.bad, true, nullptr, true, fte_d_upper(d));
   ACS_HIP(ctx, hipGetLastError());
   const size_t bytes = sizeof(double) * (size_t)d.nblk * d.BP * d.BP;
@@ -4046,6 +4076,40 @@ int acs_fte_debug_blocks(acs_ctx* ctx, const int32_t* skel_ints, int64_t n_ints,
     dims[0] = d.nblk;
     dims[1] = d.BP;
     dims[2] = L;
+  }
+  return ACS_OK;
+}
+
+// Test hook (include/acinoset_hip.h): which kernels and grids acs_fte_solve picks for a problem
+// of this size, from the functions the solve itself calls (fte_shape, lin_kernel, cr_asm_threads,
+// cr_level_counts, cr_nsplit, cr_level_deep). Host only: no device memory, no launch.
+int acs_fte_debug_plan(acs_ctx* ctx, int32_t n_cu, int32_t n_frames, int32_t P, int32_t n_cams,
+                       int32_t shutter_delay, int32_t sd_mode, int32_t* head, int32_t* levels, int32_t max_levels) {
+  if (n_cu <= 0 && ctx) n_cu = ctx->n_cu;
+  if (!head || n_cu <= 0 || n_frames < 2 || P < 3 || P > FK_MAXP || n_cams < 1 || n_cams > FTE_MAXC ||
+      (sd_mode != 0 && sd_mode != 1) || 3 * P > CR_MAXBP || (max_levels > 0 && !levels))
+    return ACS_E_INVALID;
+  FteDims d;
+  std::memset(&d, 0, sizeof(d));
+  fte_shape(d, n_frames, P, n_cams, shutter_delay ? 1 : 0, sd_mode);
+  head[0] = d.nblk;
+  head[1] = d.nlev;
+  head[2] = d.BP;
+  head[3] = d.GR;
+  head[4] = d.Cg;
+  head[5] = d.var ? 0 : cr_asm_threads(d.nblk, n_cu);  // 0: k_fte_assemble + k_cr_build
+  head[6] = lin_kernel(d.N) == (LinKernel)k_fte_linearize<5> ? 5 : 4;
+  head[7] = fte_d_upper(d) ? 1 : 0;
+  int sl = 1;
+  for (int lv = 0; lv < d.nlev && lv < max_levels; ++lv, sl <<= 1) {  // as cr_reduce
+    int ne, ns;
+    cr_level_counts(0, d.nblk, d.nblk - 1, sl, &ne, &ns);
+    if (ns && cr_defer() && ne * cr_nsplit(d, ne, ns) + ns > 256) ns = 0;
+    const int nsplit = cr_nsplit(d, ne, ns);
+    levels[4 * lv + 0] = ne;
+    levels[4 * lv + 1] = ns;
+    levels[4 * lv + 2] = nsplit;
+    levels[4 * lv + 3] = cr_level_deep(d.BP, 2 * (d.BP >> 4) + d.GR / 16, nsplit) ? 1 : 0;
   }
   return ACS_OK;
 }
@@ -4267,7 +4331,8 @@ static int dist_phase1_body(acs_fte_dist* h, double* p1) {
                          b.gmaxt);
       cr_launch_build(d, s, top - h->a0 + 1, b.st, b.Ab, b.gb, b.Bt, b.Dc, b.Ec, b.GBc, h->a0, h->a0, h->bend, b.Adiag);
     } else {
-      cr_launch_assemble_build(d, s, b, h->a0, top - h->a0 + 1, h->own_lo, h->own_hi, h->a0, h->bend, b.Adiag, b.graw);
+      cr_launch_assemble_build(d, h->S.n_cu, s, b, h->a0, top - h->a0 + 1, h->own_lo, h->own_hi, h->a0, h->bend,
+                               b.Adiag, b.graw);
     }
     const double* Efin = dist_local_cr(h);
     hipLaunchKernelGGL(k_cr_tau_partial, dim3(CR_NCHUNK), dim3(512), 0, s, d, b.st, b.Hloc, b.gloc, b.Tau, b.part,

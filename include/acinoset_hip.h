@@ -199,6 +199,17 @@ int acs_fte_debug_blocks(acs_ctx* ctx, const int32_t* skel_ints, int64_t n_ints,
                          const double* qinv, int32_t sd_mode, int32_t intermode, const double* X,
                          const double* tau, double lam, int32_t levels, double* D_out, int64_t* dims,
                          uint32_t flags);
+/* Test hook, host only (no device memory, no launch): the kernels and grids acs_fte_solve
+ * picks for n_frames frames of a P-parameter skeleton seen by n_cams cameras, computed by the
+ * functions the solve itself dispatches with. n_cu > 0: the CU count to plan for (ctx may be
+ * NULL); n_cu <= 0: the context's device.
+ * head[8] = {n_blk, n_lev, BP, GR, Cg, assembly (512 / 1024: k_cr_assemble_build's threads; 0:
+ * k_fte_assemble + k_cr_build, the variable-delay mode), k_fte_linearize instance (4 / 5), D
+ * stored as upper tiles (0 / 1)}; levels[4 l ..] = {blocks eliminated, survivor workgroups,
+ * nsplit, deep path (0 / 1)} of reduction level l < min(n_lev, max_levels). */
+int acs_fte_debug_plan(acs_ctx* ctx, int32_t n_cu, int32_t n_frames, int32_t P, int32_t n_cams,
+                       int32_t shutter_delay, int32_t sd_mode, int32_t* head, int32_t* levels,
+                       int32_t max_levels);
 
 /* ---- §8(e): frame-window distributed FTE (configs[3]) --------------------------------
  * One handle per rank (rank of world); every rank gets the full-size inputs of
