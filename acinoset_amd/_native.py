@@ -42,7 +42,7 @@ SYMBOLS = (
     'acs_fte_debug_blocks', 'acs_fte_debug_plan',
     'acs_sba_ext_dist_create', 'acs_sba_ext_dist_init', 'acs_sba_ext_dist_round', 'acs_sba_ext_dist_poll',
     'acs_sba_ext_dist_result', 'acs_sba_ext_dist_destroy', 'acs_ekf_run',
-    'acs_sba_ekf_pipeline',
+    'acs_sba_ekf_pipeline', 'acs_fte_covariance',
 )
 
 
@@ -112,6 +112,11 @@ class FteReport(C.Structure):
         return d
 
 
+class FteCovReport(C.Structure):
+    _fields_ = [('n_bad_pivots', C.c_int32), ('n_tau_free', C.c_int32), ('var_min', C.c_double),
+                ('var_max', C.c_double)]
+
+
 class SbaExtOpts(C.Structure):
     _fields_ = [('max_iters', C.c_int32), ('reserved', C.c_int32), ('f_scale', C.c_double), ('ftol', C.c_double),
                 ('xtol', C.c_double), ('gtol', C.c_double), ('lambda0', C.c_double)]
@@ -162,6 +167,8 @@ def _declare(lib):
                                     C.POINTER(FteOpts), C.POINTER(FteReport), u32]),
         'acs_fte_eval': (C.c_int, [_P, _P, i64, _P, i64, _P, i32, _P, _P, i32, i32, dbl, _P, i32, i32, _P, _P,
                                    _P, _P, _P, u32]),
+        'acs_fte_covariance': (C.c_int, [_P, _P, i64, _P, i64, _P, i32, _P, _P, i32, i32, dbl, _P, i32, i32, _P, _P,
+                                         _P, _P, _P, C.POINTER(FteCovReport), u32]),
         'acs_fte_debug_blocks': (C.c_int, [_P, _P, i64, _P, i64, _P, i32, _P, _P, i32, i32, dbl, _P, i32, i32, _P, _P,
                                            dbl, i32, _P, C.POINTER(i64), u32]),
         'acs_fte_debug_plan': (C.c_int, [_P, i32, i32, i32, i32, i32, i32, C.POINTER(i32), C.POINTER(i32), i32]),
@@ -622,6 +629,46 @@ class Context:
                                          _ptr(H), 0),
                    'acs_fte_eval')
         return cost, grad, H
+
+    def fte_covariance(self, table, cams, meas, w, Ts, qinv, X, tau=None, shutter_delay=True, intermode=1,
+                       markers=False, sd_mode=0):
+        """acs_fte_covariance: the blocks of the inverse of the undamped GN normal matrix at (X, tau)
+        (held delays removed). Returns a dict: x_cov (N + 2, P, P), rows as X; tau_cov (C, C), held
+        rows / columns zero; marker_cov (N, L, 3, 3) if `markers` else None; and the report fields
+        n_bad_pivots, n_tau_free, var_min, var_max. Constant or no shutter delay only."""
+        ints, reals, cams, meas, w, qinv, N, Cn = self._fte_args(table, cams, meas, w, Ts, qinv, shutter_delay,
+                                                                 intermode)
+        sd_mode = SD_MODES.get(sd_mode, sd_mode)
+        X = _c64(X).reshape(N + 2, table.P)
+        tau = self._tau_init(tau, N, Cn, sd_mode)
+        x_cov = np.empty((N + 2, table.P, table.P))
+        tau_cov = np.empty((Cn, Cn))
+        marker_cov = np.empty((N, table.L, 3, 3)) if markers else None
+        rep = FteCovReport()
+        self.check(self.lib.acs_fte_covariance(self.h, _ptr(ints), len(ints), _ptr(reals), len(reals), _ptr(cams), Cn,
+                                               _ptr(meas), _ptr(w), N, int(bool(shutter_delay)), float(Ts),
+                                               _ptr(qinv), int(sd_mode), int(intermode), _ptr(X), _ptr(tau),
+                                               _ptr(x_cov), _ptr(tau_cov), _ptr(marker_cov), C.byref(rep), 0),
+                   'acs_fte_covariance')
+        return dict(x_cov=x_cov, tau_cov=tau_cov, marker_cov=marker_cov, n_bad_pivots=int(rep.n_bad_pivots),
+                    n_tau_free=int(rep.n_tau_free), var_min=float(rep.var_min), var_max=float(rep.var_max))
+
+    def fte_covariance_dev(self, table_ints_p, n_ints, table_reals_p, n_reals, cams_p, n_cams, meas_p, w_p, N,
+                           shutter_delay, Ts, qinv_p, intermode, X_p, tau_p, x_cov_p, tau_cov_p=None,
+                           marker_cov_p=None, report=False):
+        """Device-pointer variant (every array resident in HBM, outputs written there; asynchronous
+        on the context stream unless `report`, which waits and returns the report dict)."""
+        v = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+        rep = FteCovReport() if report else None
+        self.check(self.lib.acs_fte_covariance(self.h, v(table_ints_p), n_ints, v(table_reals_p), n_reals, v(cams_p),
+                                               n_cams, v(meas_p), v(w_p), N, int(bool(shutter_delay)), float(Ts),
+                                               v(qinv_p), 0, int(intermode), v(X_p), v(tau_p), v(x_cov_p),
+                                               v(tau_cov_p), v(marker_cov_p), C.byref(rep) if report else None,
+                                               ACS_DEVICE_PTRS), 'acs_fte_covariance')
+        if not report:
+            return None
+        return dict(n_bad_pivots=int(rep.n_bad_pivots), n_tau_free=int(rep.n_tau_free), var_min=float(rep.var_min),
+                    var_max=float(rep.var_max))
 
     def fte_debug_blocks(self, table, cams, meas, w, Ts, qinv, X, tau=None, lam=0.0, levels=0, shutter_delay=True,
                          intermode=1):

@@ -92,28 +92,45 @@ def states_from_solution(X, tau, Ts, shutter_delay, N):
 
 
 def solve(meas, w, camera_params, mode, fps, X0, shutter_delay=True, interpolation_mode='vel', tau0=None,
-          ctx=None, shutter_delay_mode='const', **opts):
+          ctx=None, shutter_delay_mode='const', covariance=False, **opts):
     """Array-level FTE solve. meas (N,C,L,2), w (N,C,L); returns (X (N+2,P), tau, report) with
-    tau (C,) for shutter_delay_mode 'const' and (N, C) for 'variable'."""
+    tau (C,) for shutter_delay_mode 'const' and (N, C) for 'variable'. covariance=True: the
+    report gains x_cov (N+2,P,P), tau_cov (C,C), marker_cov (N,L,3,3) and cov_bad_pivots, the
+    covariance of the estimate at the solution (acs_fte_covariance; 'const' or no delay)."""
     k_arr, d_arr, r_arr, t_arr = camera_params[:4]
     n = len(k_arr)
     cams = _native.pack_cameras(k_arr, np.asarray(d_arr).reshape(n, 4), r_arr, np.asarray(t_arr).reshape(n, 3))
+    if covariance and shutter_delay and shutter_delay_mode == 'variable':
+        raise ValueError("covariance=True needs shutter_delay_mode 'const' or no shutter delay, not 'variable'")
     ctx = ctx or _native.default_context()
     o = ctx.fte_default_opts(**opts)
     im = INTERMODES[interpolation_mode] if shutter_delay else 0
-    return ctx.fte_solve(build_table(mode), cams, meas, w, 1.0 / float(fps), model_weights(mode), X0, tau0,
-                         shutter_delay=shutter_delay, intermode=im, opts=o, sd_mode=shutter_delay_mode)
+    table, Ts, qinv = build_table(mode), 1.0 / float(fps), model_weights(mode)
+    X, tau, rep = ctx.fte_solve(table, cams, meas, w, Ts, qinv, X0, tau0, shutter_delay=shutter_delay, intermode=im,
+                                opts=o, sd_mode=shutter_delay_mode)
+    if covariance:
+        cov = ctx.fte_covariance(table, cams, meas, w, Ts, qinv, X, tau, shutter_delay=shutter_delay, intermode=im,
+                                 markers=True, sd_mode=shutter_delay_mode)
+        rep.update(x_cov=cov['x_cov'], tau_cov=cov['tau_cov'], marker_cov=cov['marker_cov'],
+                   cov_bad_pivots=cov['n_bad_pivots'])
+    return X, tau, rep
 
 
 def fte(OUT_DIR, points_2d_df, mode, camera_params, start_frame, end_frame, dlc_thresh, scene_fpath,
         params: Dict = {}, shutter_delay: bool = False, shutter_delay_mode: str = 'const',
-        interpolation_mode: str = 'pos', video: bool = True, plot: bool = False, **solver_opts) -> str:
+        interpolation_mode: str = 'pos', video: bool = True, plot: bool = False, covariance: bool = False,
+        **solver_opts) -> str:
+    """covariance=True adds to fte.pickle the covariance of the estimate (the inverse of the
+    Gauss-Newton normal matrix at the solution): x_cov (N, P, P) aligned with x,
+    shutter_delay_cov (C, C) and positions_cov (N, L, 3, 3) of the marker positions."""
     sd, sd_mode, intermode = shutter_delay, shutter_delay_mode, interpolation_mode
     if sd:
         assert sd_mode == 'const' or sd_mode == 'variable'
         assert intermode == 'vel' or intermode == 'acc'
     else:
         assert intermode == 'pos'
+    if covariance and sd and sd_mode == 'variable':
+        raise ValueError("covariance=True needs shutter_delay_mode 'const' or no shutter delay, not 'variable'")
     os.makedirs(OUT_DIR, exist_ok=True)
     app.start_logging(os.path.join(OUT_DIR, 'fte.log'))
     try:
@@ -136,7 +153,8 @@ def fte(OUT_DIR, points_2d_df, mode, camera_params, start_frame, end_frame, dlc_
         print('----- Optimization (GPU LM) -----')
         t0 = time()
         X, tau, rep = solve(meas, w, (k_arr, d_arr, r_arr, t_arr), mode, params['vid_fps'], X0, sd, intermode,
-                            shutter_delay_mode=sd_mode, **solver_opts)
+                            shutter_delay_mode=sd_mode, covariance=covariance, **solver_opts)
+        cov = {k: rep.pop(k) for k in ('x_cov', 'tau_cov', 'marker_cov')} if covariance else None
         print(f"status {rep['status_name']}, {rep['iters']} iterations, cost {rep['cost_before']:.6e} -> "
               f"{rep['cost_after']:.6e}")
         print('\nOptimization took {0:.2f} seconds\n'.format(time() - t0))
@@ -157,6 +175,10 @@ def fte(OUT_DIR, points_2d_df, mode, camera_params, start_frame, end_frame, dlc_
             'z': pos[:, :len(markers), 2].T.ravel()}))
     pix_errors = metric.residual_error(points_2d_df, points_3d_dfs, markers, camera_params)
     states['reprj_errors'] = pix_errors
+    if covariance:
+        states['x_cov'] = cov['x_cov'][2:]
+        states['shutter_delay_cov'] = cov['tau_cov']
+        states['positions_cov'] = cov['marker_cov']
     # fte.pickle keeps the reference's schema (src/core/fte.py:540-579); the LM report (status,
     # iterations, costs) goes beside it
     with open(os.path.join(OUT_DIR, 'solver_report.json'), 'w') as f:

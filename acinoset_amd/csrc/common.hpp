@@ -42,6 +42,10 @@ struct acs_ctx {
   // its own allocation, so that a device-pointer call can be checked after the fact
   // (acs_ekf_singular_count) whatever the workspace slots did since
   int* ekf_bad = nullptr;
+  // factors and covariance blocks of acs_fte_covariance (fte_cov.hpp), allocated on first use
+  // and kept: its own allocation, so the solve's workspace slots stay as they are
+  void* fte_cov = nullptr;
+  size_t fte_cov_bytes = 0;
 };
 
 // Every device / pinned-host allocation and free the library makes goes through these, and

@@ -150,6 +150,7 @@ int acs_ctx_destroy(acs_ctx* ctx) {
     if (ctx->ws[i]) (void)acs_dev_free(ctx->ws[i]);
   if (ctx->pinned) (void)acs_host_free(ctx->pinned);
   if (ctx->ekf_bad) (void)acs_dev_free(ctx->ekf_bad);
+  if (ctx->fte_cov) (void)acs_dev_free(ctx->fte_cov);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
   delete ctx;
   return ACS_OK;

@@ -4124,6 +4124,9 @@ void acs_fte_back_trace_read(unsigned long long* out) {
 #endif
 }  // extern "C"
 
+// acs_fte_covariance: selected inversion of the undamped normal matrix (its own kernels)
+#include "fte_cov.hpp"
+
 // ---------------------------------------------------------------------------------------
 // distributed handle API (include/acinoset_hip.h, §8(e)); payloads are device pointers
 // ---------------------------------------------------------------------------------------

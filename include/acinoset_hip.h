@@ -188,6 +188,33 @@ int acs_fte_eval(acs_ctx* ctx, const int32_t* skel_ints, int64_t n_ints, const d
                  const double* w, int32_t n_frames, int32_t shutter_delay, double Ts,
                  const double* qinv, int32_t sd_mode, int32_t intermode, const double* X,
                  const double* tau, double* cost3, double* grad, double* H, uint32_t flags);
+/* Covariance of the FTE estimate at (X, tau): cov = the matching blocks of the inverse of the
+ * undamped GN normal matrix H that acs_fte_eval returns at (X, tau), with the held delays
+ * removed (camera 0, and a delay on a bound of [-Ts, Ts] whose descent direction points out:
+ * constants, as in an LM step). The blocks are read off the solve's block cyclic reduction
+ * tree (selected inversion); the dense inverse is never formed.
+ * cov_x (n_frames + 2, P, P): per-row pose covariance, rows as X; cov_tau (C, C), may be NULL:
+ * the delays' covariance, held rows and columns zero, all zeros without shutter_delay;
+ * cov_marker (n_frames, L, 3, 3), may be NULL: J cov_x[k + 2] J^T per frame k and marker, J the
+ * Jacobian of the marker position (acs_fk's jac) at X row k + 2 alone (no delay shift, no
+ * direction markers). Arguments up to intermode exactly as acs_fte_eval; host pointers, or
+ * ACS_DEVICE_PTRS for every array (then asynchronous unless `report` is given).
+ * Non-positive pivots (H not positive definite) are counted in the report, never clamped away.
+ * sd_mode 1 ('variable') returns ACS_E_INVALID: the per-frame delays are eliminated inside the
+ * block build and their covariances need a back-substitution of their own (not built yet).
+ * The factors and covariance blocks (about 4 BP^2 + 2 BP GR doubles per super-block) are
+ * allocated on first use and kept in the context. Single GPU only.                          */
+typedef struct {
+  int32_t n_bad_pivots;  /* non-positive pivots met (0 for a positive definite H) */
+  int32_t n_tau_free;    /* delays treated as unknowns */
+  double var_min, var_max;  /* extreme diagonal entries of cov_x over rows 2.. */
+} acs_fte_cov_report;
+int acs_fte_covariance(acs_ctx* ctx, const int32_t* skel_ints, int64_t n_ints, const double* skel_reals,
+                       int64_t n_reals, const double* cams, int32_t n_cams, const double* meas,
+                       const double* w, int32_t n_frames, int32_t shutter_delay, double Ts,
+                       const double* qinv, int32_t sd_mode, int32_t intermode, const double* X,
+                       const double* tau, double* cov_x, double* cov_tau, double* cov_marker,
+                       acs_fte_cov_report* report, uint32_t flags);
 /* Test hook: the damped 3-frame super-blocks D_i (n_blk x BP x BP, BP = 3P padded to 16) of
  * acs_fte_solve's block-tridiagonal system at (X, tau) with damping lam, after `levels`
  * cyclic-reduction levels with every pending Schur term applied (0: as assembled; L > 0:
