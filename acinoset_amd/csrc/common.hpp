@@ -239,9 +239,12 @@ __device__ __forceinline__ void fisheye_uvj(const double* __restrict__ c, double
   u = c[0] * (a * s) + c[2];
   v = c[1] * (b * s) + c[3];
   const double dthd = 1.0 + th2 * (3.0 * k1 + th2 * (5.0 * k2 + th2 * (7.0 * k3 + th2 * 9.0 * k4)));
-  double keep = big ? 1.0 : 0.0;  // opaque 0 / 1 factor, as in fisheye_project
-  asm volatile("" : "+v"(keep));
-  const double spr = (dthd * r * rcp_nr(1.0 + r2) - thd) * (ir * ir * ir) * keep;
+  // zero below the guard by two selects of the result (there the product is exactly 0, as in
+  // fisheye_project); the product is opaque to the compiler so that it does not turn the
+  // selects back into a branch around the reciprocal
+  double sprb = (dthd * r * rcp_nr(1.0 + r2) - thd) * (ir * ir * ir);
+  asm volatile("" : "+v"(sprb));
+  const double spr = big ? sprb : 0.0;
   const double ab = a * b * spr;
   const double fu = c[0] * iz, fv = c[1] * iz;
   const double ua = fu * (s + a * a * spr), ub = fu * ab;  // iz du/da, iz du/db

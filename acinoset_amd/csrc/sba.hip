@@ -27,6 +27,35 @@
 
 #include "common.hpp"
 
+// The ten sums of one linearisation (6 H, 3 g, the cost) inside an aligned group of G lanes,
+// issued stage by stage: every value takes stage 1, then every value stage 2, and so on, so
+// that no DPP move reads a register the add just before it wrote (a read-after-write hazard
+// the hardware covers with s_nop wait states: issue slots of the lone wave). The additions and
+// their order are those of group_sum<G> on each value. The last stage's addition is left to
+// the caller for the first nine (v[i] + p[i] is the total): the LM pass adds them only where
+// the step is accepted; v[9], the cost, is complete.
+template <int G, int K>
+__device__ __forceinline__ double group_partner(double v) {
+  if constexpr (K == 0) return dpp_f64<0xB1>(v);        // quad_perm [1,0,3,2]
+  else if constexpr (K == 1) return dpp_f64<0x4E>(v);   // quad_perm [2,3,0,1]
+  else if constexpr (K == 2) return dpp_f64<0x141>(v);  // row_half_mirror
+  else if constexpr (K == 3) return dpp_f64<0x140>(v);  // row_mirror
+  else return __shfl_xor(v, 1 << K, G);
+}
+template <int G, int K = 0>
+__device__ __forceinline__ void group_sum10(double (&v)[10], double (&p)[9]) {
+  constexpr bool last = (2 << K) == G;
+#pragma unroll
+  for (int i = 0; i < 10; ++i) {
+    const double q = group_partner<G, K>(v[i]);
+    if (last && i < 9)
+      p[i] = q;
+    else
+      v[i] += q;
+  }
+  if constexpr (!last) group_sum10<G, K + 1>(v, p);
+}
+
 struct SbaParams {
   int max_iters;
   double f_scale, ftol, xtol, gtol;
@@ -50,8 +79,13 @@ __global__ __launch_bounds__(256) void k_sba_lm(const double* __restrict__ cams,
                                                 double* __restrict__ cost0, double* __restrict__ cost1,
                                                 int* __restrict__ stat) {
   extern __shared__ double s_cam[];
+  // every kernel argument the address computations need, requested before the first scalar
+  // wait: left alone, the compiler loads each where the first branch that uses it begins,
+  // three dependent scalar-load rounds ahead of the two vector rounds
+  const unsigned bdim = blockDim.x;
+  asm volatile("" ::"s"(cams), "s"(uv), "s"(mask), "s"(pts_in), "s"(n_pts), "s"(C), "s"(K), "s"(bdim));
   const int lane = threadIdx.x & (G - 1);
-  const int64_t p = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / G;
+  const int64_t p = ((int64_t)blockIdx.x * bdim + threadIdx.x) / G;
   const bool live = p < n_pts;
   // every global load is issued before the first wait: the slot's observation, its mask and
   // camera id, and the point (none depends on another), then the camera records for LDS.
@@ -151,11 +185,12 @@ __global__ __launch_bounds__(256) void k_sba_lm(const double* __restrict__ cams,
   // One pass over the observations at X: robust cost, Triggs-weighted GN matrix (packed
   // upper 3x3) and IRLS gradient, group-reduced. The trial point of every LM iteration is
   // linearised speculatively, so an accepted step (the common case) costs one projection.
-  auto linearize = [&](double X0, double X1, double X2, double* Ho, double* go, double& Fo) {
+  auto linearize = [&](double X0, double X1, double X2, double (&v)[10], double (&vp)[9], double& Fo) {
+    double Ho[6], go[3];
 #pragma unroll
     for (int i = 0; i < 6; ++i) Ho[i] = 0.0;
     go[0] = go[1] = go[2] = 0.0;
-    double Fl = 0.0;
+    double Fl;
     // S > 1: the lane's slots share one logarithm too. With T = prod_s (1 + t_s) - 1 formed as
     // T + t + T t (exact algebra, relative rounding only), sum_s log1p(t_s) = log1p(T), and
     // prod_s 1 / (1 + t_s) is the reciprocal it needs. An empty slot (t = 0, 1 / (1 + t) = 1)
@@ -175,7 +210,7 @@ __global__ __launch_bounds__(256) void k_sba_lm(const double* __restrict__ cams,
       // the logarithm's own reciprocal of (1 + zu)(1 + zv)
       const double t = zu + zv + zu * zv, u1 = 1.0 + t, ru = rcp_nr(u1);
       if constexpr (S == 1) {
-        Fl += log1p_pos_ur(t, u1, ru);
+        Fl = log1p_pos_ur(t, u1, ru);
       } else {
         Tl = s == 0 ? t : fma(Tl, t, Tl + t);
         rTl = s == 0 ? ru : rTl * ru;
@@ -201,14 +236,25 @@ __global__ __launch_bounds__(256) void k_sba_lm(const double* __restrict__ cams,
     }
     if constexpr (S > 1) Fl = log1p_pos_ur(Tl, 1.0 + Tl, rTl);
 #pragma unroll
-    for (int i = 0; i < 6; ++i) Ho[i] = group_sum<G>(Ho[i]);
+    for (int i = 0; i < 6; ++i) v[i] = Ho[i];
 #pragma unroll
-    for (int i = 0; i < 3; ++i) go[i] = group_sum<G>(go[i]);
-    Fo = 0.5 * f2 * group_sum<G>(Fl);
+    for (int i = 0; i < 3; ++i) v[6 + i] = go[i];
+    v[9] = Fl;
+    group_sum10<G>(v, vp);
+    Fo = 0.5 * f2 * v[9];
+    // the cost is this rounded product wherever it is used: not fused into F - Fn of the ftol test
+    asm("" : "+v"(Fo));
   };
 
   double H[6], g[3], F;
-  linearize(x0, x1, x2, H, g, F);
+  {
+    double v[10], vp[9];
+    linearize(x0, x1, x2, v, vp, F);
+#pragma unroll
+    for (int i = 0; i < 6; ++i) H[i] = v[i] + vp[i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) g[i] = v[6 + i] + vp[6 + i];
+  }
   const double F_before = F;
   double lam = 1e-3;
   int status = ACS_STATUS_RUNNING, iters = 0, nfev = 1;
@@ -218,6 +264,15 @@ __global__ __launch_bounds__(256) void k_sba_lm(const double* __restrict__ cams,
   // positive definite) is a predicate on the same code, not a path of its own.
   while (true) {
     const double gmax = fmax(fabs(g[0]), fmax(fabs(g[1]), fabs(g[2])));
+    // |x| for the xtol test of this pass depends on x alone: formed here, its reciprocal square
+    // root (a seed and seven dependent operations) issues in the stalls of the Cholesky's own
+    // dependent chain instead of standing as a chain of its own behind the trial.
+    // |x| = xx / sqrt(xx) without a branch or select for xx = 0: the smallest normal number
+    // stands in for it, and 0 times its finite reciprocal root is exactly 0 (an xx below it
+    // is an |x| below 1.5e-154, which xtol + |x| rounds away either way)
+    const double xx = x0 * x0 + x1 * x1 + x2 * x2;
+    double xs = prm.xtol + xx * rsq_nr(fmax(xx, 2.2250738585072014e-308));  // xtol + |x|
+    asm volatile("" : "+v"(xs));  // stays here: not sunk behind the first exit again
     // Cholesky of H + lam*diag(H)
     const double dl = 1.0 + lam;
     const double a00 = H[0] * dl, a11 = H[3] * dl, a22 = H[5] * dl;
@@ -243,42 +298,55 @@ __global__ __launch_bounds__(256) void k_sba_lm(const double* __restrict__ cams,
     // addition of the rounded step, never a multiply-add fused with the last product above)
     asm volatile("" : "+v"(dx0), "+v"(dx1), "+v"(dx2));
     // model decrease of the step, -g.dx - dx.H.dx/2: below the resolution of the
-    // float64 cost the step can only be accepted or rejected by rounding -> converged
-    const double Hd0 = H[0] * dx0 + H[1] * dx1 + H[2] * dx2;
-    const double Hd1 = H[1] * dx0 + H[3] * dx1 + H[4] * dx2;
-    const double Hd2 = H[2] * dx0 + H[4] * dx1 + H[5] * dx2;
-    const double pred = -(g[0] * dx0 + g[1] * dx1 + g[2] * dx2) - 0.5 * (dx0 * Hd0 + dx1 * Hd1 + dx2 * Hd2);
+    // float64 cost the step can only be accepted or rejected by rounding -> converged.
+    // From the damped system the step solves, (H + lam D) dx = -g with D = diag(H):
+    // dx.H.dx = -g.dx - lam dx.D.dx, so the decrease is sum_i dx_i (lam H_ii dx_i - g_i) / 2,
+    // no H.dx and no difference of two nearly equal sums. Only used under pd, where the step
+    // is that solution.
+    const double pred = 0.5 * (dx0 * (lam * H[0] * dx0 - g[0]) + dx1 * (lam * H[3] * dx1 - g[1]) +
+                               dx2 * (lam * H[5] * dx2 - g[2]));
     // first exit: max_iters, gtol or the cost resolution; which of them is sorted out after
     // the loop (status is still RUNNING here), not with three selects in every pass
     if ((iters >= max_iters) | (gmax <= prm.gtol) | (pd & (pred <= ACS_COST_RES * F))) break;
     ++iters;
     const double n0 = x0 + dx0, n1 = x1 + dx1, n2 = x2 + dx2;
-    double Hn[6], gn[3], Fn;
-    linearize(n0, n1, n2, Hn, gn, Fn);
+    double vn[10], vq[9], Fn;
+    linearize(n0, n1, n2, vn, vq, Fn);
     // not positive definite: no step, so the trial does not count, there is no xtol test, and
     // lam rises as for a rejection
     nfev += pd ? 1 : 0;
     // |dx| <= xtol (xtol + |x|), compared squared
-    const double xx = x0 * x0 + x1 * x1 + x2 * x2;
-    // |x| = xx / sqrt(xx) without a branch or select for xx = 0: the smallest normal number
-    // stands in for it, and 0 times its finite reciprocal root is exactly 0 (an xx below it
-    // is an |x| below 1.5e-154, which xtol + |x| rounds away either way)
-    const double xn = xx * rsq_nr(fmax(xx, 2.2250738585072014e-308));
-    const double xb = prm.xtol * (prm.xtol + xn);
+    const double xb = prm.xtol * xs;
     const bool small = pd && dx0 * dx0 + dx1 * dx1 + dx2 * dx2 <= xb * xb;
     const bool acc = pd && Fn < F;
     const bool fconv = acc && (F - Fn) <= prm.ftol * F;
     lam = acc ? fmax(lam * 0.1, 1e-15) : lam * 10.0;
-    if (acc) {
-      x0 = n0;
-      x1 = n1;
-      x2 = n2;
-      F = Fn;
-#pragma unroll
-      for (int i = 0; i < 6; ++i) H[i] = Hn[i];
-      g[0] = gn[0];
-      g[1] = gn[1];
-      g[2] = gn[2];
+    // An accepted step, without a branch and without a copy: x and F move once and the last
+    // stage of the nine H and g sums is added, all into their own registers (tied operands)
+    // under the exec mask of the accepting lanes, so that "keep the old value" is the absence
+    // of a write. Written as assignments under if (acc), the compiler keeps a second copy of
+    // x and F for the loop's two exits (four moves before the trial, four in the block and
+    // four behind it, in every pass) and pays the branch's mask bookkeeping around it.
+    {
+      const unsigned long long am = __ballot(acc);
+      unsigned long long sv;
+      asm("s_and_saveexec_b64 %[sv], %[am]\n\t"
+          "v_mov_b64 %[x0], %[n0]\n\tv_mov_b64 %[x1], %[n1]\n\tv_mov_b64 %[x2], %[n2]\n\t"
+          "v_mov_b64 %[F], %[Fn]\n\t"
+          "v_add_f64 %[h0], %[a0], %[b0]\n\tv_add_f64 %[h1], %[a1], %[b1]\n\t"
+          "v_add_f64 %[h2], %[a2], %[b2]\n\tv_add_f64 %[h3], %[a3], %[b3]\n\t"
+          "v_add_f64 %[h4], %[a4], %[b4]\n\tv_add_f64 %[h5], %[a5], %[b5]\n\t"
+          "v_add_f64 %[g0], %[a6], %[b6]\n\tv_add_f64 %[g1], %[a7], %[b7]\n\t"
+          "v_add_f64 %[g2], %[a8], %[b8]\n\t"
+          "s_mov_b64 exec, %[sv]"
+          : [x0] "+v"(x0), [x1] "+v"(x1), [x2] "+v"(x2), [F] "+v"(F), [h0] "+v"(H[0]), [h1] "+v"(H[1]),
+            [h2] "+v"(H[2]), [h3] "+v"(H[3]), [h4] "+v"(H[4]), [h5] "+v"(H[5]), [g0] "+v"(g[0]), [g1] "+v"(g[1]),
+            [g2] "+v"(g[2]), [sv] "=&s"(sv)
+          : [am] "s"(am), [n0] "v"(n0), [n1] "v"(n1), [n2] "v"(n2), [Fn] "v"(Fn), [a0] "v"(vn[0]), [a1] "v"(vn[1]),
+            [a2] "v"(vn[2]), [a3] "v"(vn[3]), [a4] "v"(vn[4]), [a5] "v"(vn[5]), [a6] "v"(vn[6]), [a7] "v"(vn[7]),
+            [a8] "v"(vn[8]), [b0] "v"(vq[0]), [b1] "v"(vq[1]), [b2] "v"(vq[2]), [b3] "v"(vq[3]), [b4] "v"(vq[4]),
+            [b5] "v"(vq[5]), [b6] "v"(vq[6]), [b7] "v"(vq[7]), [b8] "v"(vq[8])
+          : "scc");
     }
     // second exit, rising priority: stalled (lam only passes 1e16 on a pass without an
     // accepted step), xtol, ftol of an accepted step
