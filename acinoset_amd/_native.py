@@ -29,6 +29,8 @@ ACS_CAM_STRIDE = 20
 STATUS_NAMES = ('running', 'gtol', 'ftol', 'xtol', 'stalled', 'maxiter', 'noobs')
 SD_MODES = {'const': 0, 'variable': 1}        # src/core/fte.py:35 shutter_delay_mode
 
+SBA_LM_LAYOUTS = {'auto': 0, 'butterfly': 1, 'row': 2}   # ACS_SBA_LM_* of the header
+
 # exported symbols (checked by tests against include/acinoset_hip.h)
 SYMBOLS = (
     'acs_ctx_create', 'acs_ctx_destroy', 'acs_last_error', 'acs_ctx_set_stream', 'acs_ctx_sync',
@@ -42,7 +44,7 @@ SYMBOLS = (
     'acs_fte_debug_blocks', 'acs_fte_debug_plan',
     'acs_sba_ext_dist_create', 'acs_sba_ext_dist_init', 'acs_sba_ext_dist_round', 'acs_sba_ext_dist_poll',
     'acs_sba_ext_dist_result', 'acs_sba_ext_dist_destroy', 'acs_ekf_run',
-    'acs_sba_ekf_pipeline', 'acs_fte_covariance',
+    'acs_sba_ekf_pipeline', 'acs_fte_covariance', 'acs_sba_set_lm_layout', 'acs_sba_lm_layout',
 )
 
 
@@ -160,6 +162,8 @@ def _declare(lib):
                                            u32]),
         'acs_sba_points_dense_io': (C.c_int, [_P, _P, i32, _P, _P, i64, _P, _P, C.POINTER(SbaOpts),
                                               C.POINTER(Report), u32]),
+        'acs_sba_set_lm_layout': (C.c_int, [_P, i32]),
+        'acs_sba_lm_layout': (C.c_int, [_P, i32, i64, i32, C.POINTER(i32)]),
         'acs_redescending_loss': (C.c_int, [_P, _P, i64, dbl, dbl, dbl, _P, _P, u32]),
         'acs_fk': (C.c_int, [_P, _P, i64, _P, i64, _P, _P, _P, _P, i64, i32, i32, _P, _P, u32]),
         'acs_fte_default_opts': (None, [C.POINTER(FteOpts)]),
@@ -368,6 +372,20 @@ class Context:
                                            _ptr(pts), len(pts), C.byref(opts), _ptr(rb), _ptr(ra), C.byref(rep), 0),
                    'acs_sba_points')
         return pts, rb, ra, rep.as_dict()
+
+    def sba_set_lm_layout(self, layout='auto'):
+        """acs_sba_set_lm_layout (test hook): which LM kernel instance the points-only solves of this
+        context launch where both are legal (3..8 slots, no camera ids): 'auto', 'butterfly' or 'row'."""
+        self.check(self.lib.acs_sba_set_lm_layout(self.h, SBA_LM_LAYOUTS[layout]), 'acs_sba_set_lm_layout')
+
+    def sba_lm_layout(self, n_slots, n_pts, cam_ids=False):
+        """acs_sba_lm_layout -> ('butterfly' | 'row', n_cu): what a solve of this size would launch under
+        the current setting, and the CU count the selection works with."""
+        n_cu = C.c_int32(0)
+        rc = self.lib.acs_sba_lm_layout(self.h, int(n_slots), int(n_pts), int(bool(cam_ids)), C.byref(n_cu))
+        if rc < 0:
+            raise ValueError('acs_sba_lm_layout: bad arguments')
+        return {v: k for k, v in SBA_LM_LAYOUTS.items()}[rc], int(n_cu.value)
 
     def sba_points_dense(self, cams, uv, mask, pts0, opts=None):
         cams = _c64(cams)

@@ -15,6 +15,10 @@ HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 ARCH = 'gfx950'
 CFLAGS = ['-O3', '-std=c++17', '-fPIC', f'--offload-arch={ARCH}', '-I', os.path.join(REPO, 'include'),
           '-Wno-unused-result']
+# per-file flags. sba.hip: the leading kernel arguments of k_sba_lm arrive in user SGPRs at wave
+# launch (gfx950 kernel-argument preload) instead of through a scalar load of their own; the
+# compiler's compatibility prologue covers firmware without it.
+FILE_CFLAGS = {'sba.hip': ['-mllvm', '-amdgpu-kernarg-preload-count=16']}
 
 
 def _newest(paths):
@@ -34,7 +38,7 @@ def build(force: bool = False, verbose: bool = True, jobs: int = 8) -> str:
         obj = os.path.join(objdir, os.path.basename(src)[:-4] + '.o')
         if not force and os.path.exists(obj) and os.path.getmtime(obj) >= max(os.path.getmtime(src), hdr_t):
             return obj
-        cmd = [HIPCC, *CFLAGS, '-c', src, '-o', obj]
+        cmd = [HIPCC, *CFLAGS, *FILE_CFLAGS.get(os.path.basename(src), []), '-c', src, '-o', obj]
         if verbose:
             print(' '.join(cmd), flush=True)
         subprocess.run(cmd, check=True)

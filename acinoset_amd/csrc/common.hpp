@@ -46,6 +46,8 @@ struct acs_ctx {
   // and kept: its own allocation, so the solve's workspace slots stay as they are
   void* fte_cov = nullptr;
   size_t fte_cov_bytes = 0;
+  // which k_sba_lm instance run_lm takes where both are legal (acs_sba_set_lm_layout; sba.hip)
+  int sba_lm_layout = ACS_SBA_LM_AUTO;
 };
 
 // Every device / pinned-host allocation and free the library makes goes through these, and
@@ -313,4 +315,98 @@ __device__ __forceinline__ double group_sum(double v) {
   if (G >= 32) v += __shfl_xor(v, 16, G);
   if (G >= 64) v += __shfl_xor(v, 32, G);
   return v;
+}
+
+// Row-broadcast group sums of k_sba_lm's ROW instances (sba.hip; one point per 16-lane DPP row, slots in lanes 0..K-1, K <= 8): the sums behind
+// the first (quad_perm xor 1) stage are taken with row_newbcast, the one DPP control gfx950's
+// f64 VALU accepts. After stage 1 lane 2j holds the pair sum s(2j,2j+1), and for every lane
+//   v_mov_b64_dpp  t, s       row_newbcast:0   t  = s01
+//   v_fmac_f64_dpp t, s, 1.0  row_newbcast:2   t  = fma(s23, 1.0, t) = s01 + s23, rounded once
+//   v_fmac_f64_dpp t, s, 1.0  row_newbcast:4   t += s45
+// is one issue slot per term, where the butterfly pays two 32-bit DPP moves and an add per
+// stage. ROW is the number of pairs, (K + 1) / 2, and the tree is the butterfly's own:
+//   ROW 2  s01 + s23                  = group_sum<4>
+//   ROW 3  (s01 + s23) + s45          = group_sum<8>, whose s67 is the empty lanes' +0.0
+//   ROW 4  (s01 + s23) + (s45 + s67)  = group_sum<8>
+// so every sum has the bits of the butterfly instance's; the only possible difference would be
+// the sign of a sum that is exactly zero (x + (+0.0) turns -0.0 into +0.0), and a lane's value
+// is 0.0 + products here, never -0.0.
+// Hazard the assembler does not see inside an asm statement: a DPP instruction must not read a
+// VGPR that either of the two instructions before it wrote. The statements below run stage by
+// stage over their values, and start with instructions that are not DPP.
+#define ACS_ROW_BC(n) " row_newbcast:" #n " row_mask:0xf bank_mask:0xf\n\t"
+#define ACS_ROW_MOV(d, s, n) "v_mov_b64_dpp %[" #d "], %[" #s "]" ACS_ROW_BC(n)
+#define ACS_ROW_FMAC(d, s, n) "v_fmac_f64_dpp %[" #d "], %[" #s "], %[one]" ACS_ROW_BC(n)
+#define ACS_ROW_ADD(d, a, b) "v_add_f64 %[" #d "], %[" #a "], %[" #b "]\n\t"
+#define ACS_ROW_ADDT(d, t, n) ACS_ROW_ADD(d, d, t)
+#define ACS_ROW9(OP, d, s, n)                                                                             \
+  OP(d##0, s##0, n) OP(d##1, s##1, n) OP(d##2, s##2, n) OP(d##3, s##3, n) OP(d##4, s##4, n) OP(d##5, s##5, n) \
+      OP(d##6, s##6, n) OP(d##7, s##7, n) OP(d##8, s##8, n)
+// the nine H and g sums from their pair sums s0..s8 into h0..h8 (ROW 4: temporaries t0..t8);
+// the operand lists name the caller's H[6], g[3], s[9+], one and t[9]
+#define ACS_ROW_SUMS2 ACS_ROW9(ACS_ROW_MOV, h, s, 0) ACS_ROW9(ACS_ROW_FMAC, h, s, 2)
+#define ACS_ROW_SUMS3 ACS_ROW_SUMS2 ACS_ROW9(ACS_ROW_FMAC, h, s, 4)
+#define ACS_ROW_SUMS4                                                                                \
+  ACS_ROW9(ACS_ROW_MOV, h, s, 0) ACS_ROW9(ACS_ROW_MOV, t, s, 4) ACS_ROW9(ACS_ROW_FMAC, h, s, 2)      \
+  ACS_ROW9(ACS_ROW_FMAC, t, s, 6) ACS_ROW9(ACS_ROW_ADDT, h, t, 0)
+#define ACS_ROW_H(c)                                                                                       \
+  [h0] c(H[0]), [h1] c(H[1]), [h2] c(H[2]), [h3] c(H[3]), [h4] c(H[4]), [h5] c(H[5]), [h6] c(g[0]), [h7] c(g[1]), \
+      [h8] c(g[2])
+#define ACS_ROW_T                                                                                              \
+  [t0] "=&v"(t[0]), [t1] "=&v"(t[1]), [t2] "=&v"(t[2]), [t3] "=&v"(t[3]), [t4] "=&v"(t[4]), [t5] "=&v"(t[5]), \
+      [t6] "=&v"(t[6]), [t7] "=&v"(t[7]), [t8] "=&v"(t[8])
+#define ACS_ROW_S                                                                                          \
+  [s0] "v"(s[0]), [s1] "v"(s[1]), [s2] "v"(s[2]), [s3] "v"(s[3]), [s4] "v"(s[4]), [s5] "v"(s[5]), [s6] "v"(s[6]), \
+      [s7] "v"(s[7]), [s8] "v"(s[8]), [one] "v"(one)
+
+// Stage 1 of the ten sums (s[i] += q[i], q the xor-1 partner's value) and the cost's sum, which
+// the accept decision waits for, in one statement: the cost's DPP instructions stand between
+// the additions, each two instructions behind the last write of what it reads.
+template <int ROW>
+__device__ __forceinline__ double row_pairs_cost(double (&s)[10], const double (&q)[10], double one) {
+  double c, c2;
+#define ACS_ROW_PAIR(i) "v_add_f64 %[s" #i "], %[s" #i "], %[q" #i "]\n\t"
+#define ACS_ROW_PAIR_OPS                                                                                       \
+  [s0] "+v"(s[0]), [s1] "+v"(s[1]), [s2] "+v"(s[2]), [s3] "+v"(s[3]), [s4] "+v"(s[4]), [s5] "+v"(s[5]),          \
+      [s6] "+v"(s[6]), [s7] "+v"(s[7]), [s8] "+v"(s[8]), [s9] "+v"(s[9])
+#define ACS_ROW_PAIR_IN                                                                                        \
+  [q0] "v"(q[0]), [q1] "v"(q[1]), [q2] "v"(q[2]), [q3] "v"(q[3]), [q4] "v"(q[4]), [q5] "v"(q[5]), [q6] "v"(q[6]), \
+      [q7] "v"(q[7]), [q8] "v"(q[8]), [q9] "v"(q[9]), [one] "v"(one)
+  if constexpr (ROW == 2) {
+    asm(ACS_ROW_PAIR(9) ACS_ROW_PAIR(0) ACS_ROW_PAIR(1) ACS_ROW_MOV(c, s9, 0) ACS_ROW_PAIR(2) ACS_ROW_PAIR(3)
+            ACS_ROW_FMAC(c, s9, 2) ACS_ROW_PAIR(4) ACS_ROW_PAIR(5) ACS_ROW_PAIR(6) ACS_ROW_PAIR(7) ACS_ROW_PAIR(8)
+        : [c] "=&v"(c), ACS_ROW_PAIR_OPS
+        : ACS_ROW_PAIR_IN);
+  } else if constexpr (ROW == 3) {
+    asm(ACS_ROW_PAIR(9) ACS_ROW_PAIR(0) ACS_ROW_PAIR(1) ACS_ROW_MOV(c, s9, 0) ACS_ROW_PAIR(2) ACS_ROW_PAIR(3)
+            ACS_ROW_FMAC(c, s9, 2) ACS_ROW_PAIR(4) ACS_ROW_PAIR(5) ACS_ROW_FMAC(c, s9, 4) ACS_ROW_PAIR(6)
+                ACS_ROW_PAIR(7) ACS_ROW_PAIR(8)
+        : [c] "=&v"(c), ACS_ROW_PAIR_OPS
+        : ACS_ROW_PAIR_IN);
+  } else {
+    static_assert(ROW == 4, "row-broadcast sums are written out for 2, 3 and 4 lane pairs");
+    asm(ACS_ROW_PAIR(9) ACS_ROW_PAIR(0) ACS_ROW_PAIR(1) ACS_ROW_MOV(c, s9, 0) ACS_ROW_MOV(c2, s9, 4) ACS_ROW_PAIR(2)
+            ACS_ROW_FMAC(c, s9, 2) ACS_ROW_FMAC(c2, s9, 6) ACS_ROW_PAIR(3) ACS_ROW_PAIR(4) ACS_ROW_ADD(c, c, c2)
+                ACS_ROW_PAIR(5) ACS_ROW_PAIR(6) ACS_ROW_PAIR(7) ACS_ROW_PAIR(8)
+        : [c] "=&v"(c), [c2] "=&v"(c2), ACS_ROW_PAIR_OPS
+        : ACS_ROW_PAIR_IN);
+  }
+#undef ACS_ROW_PAIR
+#undef ACS_ROW_PAIR_OPS
+#undef ACS_ROW_PAIR_IN
+  return c;
+}
+
+// The nine H and g sums from the pair sums, in every lane (the first linearisation; the LM
+// pass takes them under the accepting lanes' mask, inside its accept statement).
+template <int ROW>
+__device__ __forceinline__ void row_sums9(double (&H)[6], double (&g)[3], const double (&s)[10], double one) {
+  if constexpr (ROW == 2) {
+    asm(ACS_ROW_SUMS2 : ACS_ROW_H("=&v") : ACS_ROW_S);
+  } else if constexpr (ROW == 3) {
+    asm(ACS_ROW_SUMS3 : ACS_ROW_H("=&v") : ACS_ROW_S);
+  } else {
+    double t[9];
+    asm(ACS_ROW_SUMS4 : ACS_ROW_H("=&v"), ACS_ROW_T : ACS_ROW_S);
+  }
 }

@@ -18,6 +18,9 @@
 // bit-identical sums, so all lanes take the same accept/reject decision with no LDS
 // round trip and no atomics. The whole LM loop runs inside one launch: HBM traffic is
 // the observation tensor once plus the points in and out.
+// Small dense problems (3..8 slots, at most one wave per SIMD) take the ROW instances instead:
+// one point per 16-lane DPP row and the same sums, in the butterfly's own order, by row
+// broadcast (common.hpp), bit-identical and 30 issue slots per pass shorter.
 //
 // LM spec (shared with oracle/sba.py): lam0 = 1e-3, Marquardt damping H + lam*diag(H),
 // xtol default 1e-9 (scipy's default, used by the reference, is 1e-8),
@@ -56,6 +59,8 @@ __device__ __forceinline__ void group_sum10(double (&v)[10], double (&p)[9]) {
   if constexpr (!last) group_sum10<G, K + 1>(v, p);
 }
 
+// (The row-broadcast sums of the ROW instances, row_pairs_cost / row_sums9 and the ACS_ROW_* pieces
+// of the accept statement below, are in common.hpp, where the probe under tools/probe shares them.)
 struct SbaParams {
   int max_iters;
   double f_scale, ftol, xtol, gtol;
@@ -69,20 +74,30 @@ struct SbaParams {
 // (amdgpu_waves_per_eu) ran it in 0.270 / 0.273 / 0.454 ms against 0.268-0.272 unconstrained
 // (profiles/r06/bench_sba_w*_r06h.log): three independent slot chains per lane already keep the
 // VALU issuing, and the 4-wave budget spills.
-template <int G, int S, bool CAMID, bool HOIST>
-__global__ __launch_bounds__(256) void k_sba_lm(const double* __restrict__ cams, int C, int K,
-                                                const double2* __restrict__ uv,
-                                                const uint8_t* __restrict__ mask,
-                                                const uint8_t* __restrict__ camid, int64_t n_pts,
-                                                const double* pts_in, double* pts,  // may alias
+// Parameter order: the arguments the first vector loads need come first (observation, mask,
+// point count, point, camera records, then the two counts), so that the kernel-argument preload
+// this file is built with (build.py) hands as many of them as the user SGPRs hold to the wave at
+// launch, with no scalar load and its round trip ahead of the first address.
+// ROW (0, or the number of lane pairs 2..4): the row-broadcast sums of common.hpp in place of the
+// butterfly. G = 16 (one point per DPP row), S = 1, no camera ids, HOIST only: the instance for
+// latency-bound grids, where a wave of 4 points instead of 8 costs nothing (run_lm).
+template <int G, int S, bool CAMID, bool HOIST, int ROW = 0>
+__global__ __launch_bounds__(256) void k_sba_lm(const double2* __restrict__ uv,
+                                                const uint8_t* __restrict__ mask, int64_t n_pts,
+                                                const double* pts_in, const double* __restrict__ cams,
+                                                int K, int C, const uint8_t* __restrict__ camid,
+                                                double* pts,  // may alias pts_in
                                                 SbaParams prm,
                                                 double* __restrict__ cost0, double* __restrict__ cost1,
                                                 int* __restrict__ stat) {
+  static_assert(ROW == 0 || (G == 16 && S == 1 && !CAMID && HOIST), "ROW: 16-lane rows, one slot per lane, hoisted records");
   extern __shared__ double s_cam[];
   // every kernel argument the address computations need, requested before the first scalar
   // wait: left alone, the compiler loads each where the first branch that uses it begins,
   // three dependent scalar-load rounds ahead of the two vector rounds
-  const unsigned bdim = blockDim.x;
+  // (the HOIST instances are launched in blocks of one wave: the block size is then no hidden
+  // argument to load either, and with the preload none of these is a load)
+  const unsigned bdim = HOIST ? 64u : blockDim.x;
   asm volatile("" ::"s"(cams), "s"(uv), "s"(mask), "s"(pts_in), "s"(n_pts), "s"(C), "s"(K), "s"(bdim));
   const int lane = threadIdx.x & (G - 1);
   const int64_t p = ((int64_t)blockIdx.x * bdim + threadIdx.x) / G;
@@ -240,8 +255,17 @@ __global__ __launch_bounds__(256) void k_sba_lm(const double* __restrict__ cams,
 #pragma unroll
     for (int i = 0; i < 3; ++i) v[6 + i] = go[i];
     v[9] = Fl;
-    group_sum10<G>(v, vp);
-    Fo = 0.5 * f2 * v[9];
+    if constexpr (ROW) {
+      // the compiler places the 32-bit quad_perm moves (and sees their hazards); v becomes the
+      // pair sums, vp stays unused
+      double qp[10];
+#pragma unroll
+      for (int i = 0; i < 10; ++i) qp[i] = dpp_f64<0xB1>(v[i]);
+      Fo = 0.5 * f2 * row_pairs_cost<ROW>(v, qp, 1.0);
+    } else {
+      group_sum10<G>(v, vp);
+      Fo = 0.5 * f2 * v[9];
+    }
     // the cost is this rounded product wherever it is used: not fused into F - Fn of the ftol test
     asm("" : "+v"(Fo));
   };
@@ -250,10 +274,14 @@ __global__ __launch_bounds__(256) void k_sba_lm(const double* __restrict__ cams,
   {
     double v[10], vp[9];
     linearize(x0, x1, x2, v, vp, F);
+    if constexpr (ROW) {
+      row_sums9<ROW>(H, g, v, 1.0);
+    } else {
 #pragma unroll
-    for (int i = 0; i < 6; ++i) H[i] = v[i] + vp[i];
+      for (int i = 0; i < 6; ++i) H[i] = v[i] + vp[i];
 #pragma unroll
-    for (int i = 0; i < 3; ++i) g[i] = v[6 + i] + vp[6 + i];
+      for (int i = 0; i < 3; ++i) g[i] = v[6 + i] + vp[6 + i];
+    }
   }
   const double F_before = F;
   double lam = 1e-3;
@@ -288,6 +316,8 @@ __global__ __launch_bounds__(256) void k_sba_lm(const double* __restrict__ cams,
     const double d22 = a22 - L20 * L20 - L21 * L21;
     const double i22 = rsq_nr(d22);
     const bool pd = a00 > 0.0 && d11 > 0.0 && d22 > 0.0;
+    // pd as a wave mask, for the ROW instances' accept statement
+    [[maybe_unused]] const unsigned long long pdm = ROW ? __ballot(pd) : 0ull;
     const double y0 = -g[0] * i00;
     const double y1 = (-g[1] - L10 * y0) * i11;
     const double y2 = (-g[2] - L20 * y0 - L21 * y1) * i22;
@@ -327,7 +357,34 @@ __global__ __launch_bounds__(256) void k_sba_lm(const double* __restrict__ cams,
     // of a write. Written as assignments under if (acc), the compiler keeps a second copy of
     // x and F for the loop's two exits (four moves before the trial, four in the block and
     // four behind it, in every pass) and pays the branch's mask bookkeeping around it.
-    {
+    // ROW: the nine sums themselves are taken under that mask (a row accepts or rejects as a
+    // whole, so every lane a broadcast reads is enabled): the first term's v_mov_b64_dpp is the
+    // move into H and g, and a rejected pass pays for no sum but the cost's.
+    if constexpr (ROW) {
+      // the accepting lanes as the wave mask of the comparison itself, and pd's mask formed with
+      // the solve: the ballot of their conjunction is a select and a compare more, on the chain
+      // from the cost's sum to the first instruction under the mask
+      const unsigned long long am = __builtin_amdgcn_ballot_w64(Fn < F) & pdm;
+      unsigned long long sv;
+      const double one = 1.0;
+      const double(&s)[10] = vn;
+#define ACS_ROW_ACCEPT(SUMS, ...)                                                                          \
+  asm("s_and_saveexec_b64 %[sv], %[am]\n\t"                                                                \
+      "v_mov_b64 %[x0], %[n0]\n\tv_mov_b64 %[x1], %[n1]\n\tv_mov_b64 %[x2], %[n2]\n\t"                    \
+      "v_mov_b64 %[F], %[Fn]\n\t" SUMS "s_mov_b64 exec, %[sv]"                                             \
+      : [x0] "+v"(x0), [x1] "+v"(x1), [x2] "+v"(x2), [F] "+v"(F), ACS_ROW_H("+v"), [sv] "=&s"(sv) __VA_ARGS__ \
+      : [am] "s"(am), [n0] "v"(n0), [n1] "v"(n1), [n2] "v"(n2), [Fn] "v"(Fn), ACS_ROW_S                    \
+      : "scc")
+      if constexpr (ROW == 2) {
+        ACS_ROW_ACCEPT(ACS_ROW_SUMS2);
+      } else if constexpr (ROW == 3) {
+        ACS_ROW_ACCEPT(ACS_ROW_SUMS3);
+      } else {
+        double t[9];
+        ACS_ROW_ACCEPT(ACS_ROW_SUMS4, , ACS_ROW_T);
+      }
+#undef ACS_ROW_ACCEPT
+    } else {
       const unsigned long long am = __ballot(acc);
       unsigned long long sv;
       asm("s_and_saveexec_b64 %[sv], %[am]\n\t"
@@ -498,14 +555,18 @@ static void launch_lm_t(acs_ctx* ctx, int blocks, int block, const double* cams,
   const bool hoist = S == 1 && !CAMID && G <= 16 && waves <= 8 * (int64_t)ctx->n_cu;
   if constexpr (S == 1 && !CAMID && G <= 16) {
     if (hoist) {
+      // one wave per block, the size the kernel assumes (what run_lm picks for every grid of
+      // fewer than 2 waves per SIMD anyway)
+      block = 64;
+      blocks = acs_grid(n_pts * G, block);
       hipLaunchKernelGGL((k_sba_lm<G, S, CAMID, true>), dim3(blocks), dim3(block),
-                         sizeof(double) * ACS_CAM_STRIDE * (C + 1), ctx->stream, cams, C, K, uv, mask, camid, n_pts, pts_in,
+                         sizeof(double) * ACS_CAM_STRIDE * (C + 1), ctx->stream, uv, mask, n_pts, pts_in, cams, K, C, camid,
                          pts, prm, c0, c1, st);
       return;
     }
   }
   hipLaunchKernelGGL((k_sba_lm<G, S, CAMID, false>), dim3(blocks), dim3(block), sizeof(double) * ACS_CAM_STRIDE * (C + 1),
-                     ctx->stream, cams, C, K, uv, mask, camid, n_pts, pts_in, pts, prm, c0, c1, st);
+                     ctx->stream, uv, mask, n_pts, pts_in, cams, K, C, camid, pts, prm, c0, c1, st);
 }
 
 template <int S, bool CAMID>
@@ -523,6 +584,34 @@ static int launch_lm_g(acs_ctx* ctx, int G, int blocks, int block, const double*
       return acs_fail(ctx, ACS_E_INVALID, "unsupported group size %d", G);
   }
   return ACS_OK;
+}
+
+// The row instance (k_sba_lm's ROW flag) is legal without camera ids for 3 to 8 slots (with 2
+// slots and above 8 the broadcast form is no shorter than the butterfly), and chosen for
+// latency-bound grids: at one point per 16-lane row, at most one wave per SIMD. There the
+// kernel lasts as long as its slowest wave, and the lanes a row leaves empty cost nothing.
+// ctx->sba_lm_layout (acs_sba_set_lm_layout) forces either instance where both are legal.
+static bool lm_row_selected(const acs_ctx* ctx, int K, int64_t n_pts, bool camid) {
+  const bool legal = !camid && K >= 3 && K <= 8;
+  if (!legal || ctx->sba_lm_layout == ACS_SBA_LM_BUTTERFLY) return false;
+  if (ctx->sba_lm_layout == ACS_SBA_LM_ROW) return true;
+  return (n_pts * 16 + 63) / 64 <= 4 * (int64_t)ctx->n_cu;
+}
+
+static void launch_lm_row(acs_ctx* ctx, const double* cams, int C, int K, const double2* uv, const uint8_t* mask,
+                          int64_t n_pts, const double* pts_in, double* pts, SbaParams prm, double* c0, double* c1,
+                          int* st) {
+  const dim3 grid(acs_grid(n_pts * 16, 64)), block(64);  // the block size the HOIST instances assume
+  const size_t lds = sizeof(double) * ACS_CAM_STRIDE * (C + 1);
+#define ACS_ROW_LAUNCH(r)                                                                                        \
+  hipLaunchKernelGGL((k_sba_lm<16, 1, false, true, r>), grid, block, lds, ctx->stream, uv, mask, n_pts, pts_in, cams, \
+                     K, C, (const uint8_t*)nullptr, pts, prm, c0, c1, st)
+  switch ((K + 1) / 2) {
+    case 2: ACS_ROW_LAUNCH(2); break;
+    case 3: ACS_ROW_LAUNCH(3); break;
+    default: ACS_ROW_LAUNCH(4); break;
+  }
+#undef ACS_ROW_LAUNCH
 }
 
 // Launch the LM kernel over an (n_pts, K) slot tensor already on the device; initial points
@@ -545,6 +634,14 @@ static int run_lm(acs_ctx* ctx, const double* dcams, int C, int K, const double2
     c1 = (double*)acs_ws(ctx, WS_PERPT_F1, sizeof(double) * n_pts);
     st = (int*)acs_ws(ctx, WS_PERPT_I, sizeof(int) * 3 * n_pts);
     if (!c0 || !c1 || !st) return ACS_E_NOMEM;
+  }
+  if (lm_row_selected(ctx, K, n_pts, dcamid != nullptr)) {
+    launch_lm_row(ctx, dcams, C, K, duv, dmask, n_pts, dpts_in, dpts, prm, c0, c1, st);
+    ACS_HIP(ctx, hipGetLastError());
+    *c0_out = c0;
+    *c1_out = c1;
+    *st_out = st;
+    return ACS_OK;
   }
   int G = next_pow2(K < 2 ? 2 : K);
   int S = 1;
@@ -667,6 +764,20 @@ int acs_obs_to_slots(acs_ctx* ctx, const double* duv, const int32_t* dpi, const 
 }
 
 extern "C" {
+
+int acs_sba_set_lm_layout(acs_ctx* ctx, int32_t layout) {
+  if (!ctx) return ACS_E_INVALID;
+  ACS_CHECK(ctx, layout == ACS_SBA_LM_AUTO || layout == ACS_SBA_LM_BUTTERFLY || layout == ACS_SBA_LM_ROW,
+            "acs_sba_set_lm_layout: layout %d", layout);
+  ctx->sba_lm_layout = layout;
+  return ACS_OK;
+}
+
+int acs_sba_lm_layout(const acs_ctx* ctx, int32_t n_slots, int64_t n_pts, int32_t with_cam_ids, int32_t* n_cu) {
+  if (!ctx || n_slots < 1 || n_pts < 0) return -1;
+  if (n_cu) *n_cu = ctx->n_cu;
+  return lm_row_selected(ctx, n_slots, n_pts, with_cam_ids != 0) ? ACS_SBA_LM_ROW : ACS_SBA_LM_BUTTERFLY;
+}
 
 int acs_sba_points_dense_io(acs_ctx* ctx, const double* cams, int32_t n_cams, const double* uv,
                             const uint8_t* mask, int64_t n_pts, const double* pts_in, double* pts_out,

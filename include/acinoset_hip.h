@@ -132,6 +132,21 @@ int acs_sba_points_dense_io(acs_ctx* ctx, const double* cams, int32_t n_cams, co
                             const uint8_t* mask, int64_t n_pts, const double* pts_in, double* pts_out,
                             const acs_sba_opts* opts, acs_report* report, uint32_t flags);
 
+/* Test hook: which instance of the LM kernel a points-only solve of this context launches.
+ * AUTO (the default) takes the row instance (one point per 16-lane row, row-broadcast sums) for
+ * 3..8 observation slots without camera ids when the grid is at most one wave per SIMD, else
+ * the butterfly instances; BUTTERFLY and ROW force either wherever both are legal (3..8 slots,
+ * no camera ids). The instances give bit-identical results.                               */
+#define ACS_SBA_LM_AUTO 0
+#define ACS_SBA_LM_BUTTERFLY 1
+#define ACS_SBA_LM_ROW 2
+int acs_sba_set_lm_layout(acs_ctx* ctx, int32_t layout);
+/* -> ACS_SBA_LM_BUTTERFLY or ACS_SBA_LM_ROW: what a solve of n_pts points with n_slots
+ * observation slots per point would launch under the context's setting (-1: bad arguments).
+ * n_cu (may be NULL) receives the CU count the selection works with.                        */
+int acs_sba_lm_layout(const acs_ctx* ctx, int32_t n_slots, int64_t n_pts, int32_t with_cam_ids,
+                      int32_t* n_cu);
+
 /* ---- a9: redescending loss (src/lib/misc.py:329-343), elementwise ------------------ */
 int acs_redescending_loss(acs_ctx* ctx, const double* err, int64_t n, double a, double b, double c,
                           double* out, double* dout /* d loss/d err, may be NULL */, uint32_t flags);

@@ -3,7 +3,8 @@
     hipcc <the build's flags> --cuda-device-only -S acinoset_amd/csrc/sba.hip -o sba.s
     python tools/isa_loop_slots.py sba.s [kernel-name substring]
 
-The default kernel is the headline instance k_sba_lm<8, 1, false, true>. One wave alone on a
+The default kernel is the headline instance k_sba_lm<16, 1, false, true, 3> (the row instance for
+5 or 6 slots; before round 11 the headline ran k_sba_lm<8, 1, false, true>). One wave alone on a
 SIMD issues one instruction per ~4 cycles whatever its kind, so the count of instructions is
 the figure of merit; they are classified by mnemonic only:
 
@@ -22,7 +23,7 @@ import sys
 from collections import Counter
 
 CLASSES = ('f64', 'dpp', 'vector', 'scalar', 'memory', 'other')
-DEFAULT = '_Z8k_sba_lmILi8ELi1ELb0ELb1EE'
+DEFAULT = '_Z8k_sba_lmILi16ELi1ELb0ELb1ELi3EE'
 
 
 def classify(mn):
