@@ -25,7 +25,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('ACINOSET_HIP_LIB', os.path.join(_HERE, 'libacinoset_hip.so'))
 
 ACS_DEVICE_PTRS = 1
+ACS_CAMS_STANDARD = 2      # flags bit: `cams` holds standard-model records
 ACS_CAM_STRIDE = 20
+ACS_CAM_STRIDE_STD = 24    # [fx fy cx cy k1 k2 p1 p2 k3 k4 k5 k6 R(9) t(3)]
+CAMERA_MODELS = {'fisheye': ACS_CAM_STRIDE, 'standard': ACS_CAM_STRIDE_STD}
 STATUS_NAMES = ('running', 'gtol', 'ftol', 'xtol', 'stalled', 'maxiter', 'noobs')
 SD_MODES = {'const': 0, 'variable': 1}        # src/core/fte.py:35 shutter_delay_mode
 
@@ -45,6 +48,7 @@ SYMBOLS = (
     'acs_sba_ext_dist_create', 'acs_sba_ext_dist_init', 'acs_sba_ext_dist_round', 'acs_sba_ext_dist_poll',
     'acs_sba_ext_dist_result', 'acs_sba_ext_dist_destroy', 'acs_ekf_run',
     'acs_sba_ekf_pipeline', 'acs_fte_covariance', 'acs_sba_set_lm_layout', 'acs_sba_lm_layout',
+    'acs_project_standard', 'acs_sba_lm_layout_flags',
 )
 
 
@@ -155,6 +159,7 @@ def _declare(lib):
         'acs_device_count': (C.c_int, [C.POINTER(C.c_int)]),
         'acs_sba_default_opts': (None, [C.POINTER(SbaOpts)]),
         'acs_project_fisheye': (C.c_int, [_P, _P, i32, _P, _P, i64, i32, _P, u32]),
+        'acs_project_standard': (C.c_int, [_P, _P, i32, _P, _P, i64, _P, u32]),
         'acs_sba_residuals': (C.c_int, [_P, _P, i32, _P, _P, _P, i64, _P, i64, _P, u32]),
         'acs_sba_points': (C.c_int, [_P, _P, i32, _P, _P, _P, i64, _P, i64, C.POINTER(SbaOpts), _P, _P,
                                      C.POINTER(Report), u32]),
@@ -164,6 +169,7 @@ def _declare(lib):
                                               C.POINTER(Report), u32]),
         'acs_sba_set_lm_layout': (C.c_int, [_P, i32]),
         'acs_sba_lm_layout': (C.c_int, [_P, i32, i64, i32, C.POINTER(i32)]),
+        'acs_sba_lm_layout_flags': (C.c_int, [_P, i32, i64, i32, C.POINTER(i32), u32]),
         'acs_redescending_loss': (C.c_int, [_P, _P, i64, dbl, dbl, dbl, _P, _P, u32]),
         'acs_fk': (C.c_int, [_P, _P, i64, _P, i64, _P, _P, _P, _P, i64, i32, i32, _P, _P, u32]),
         'acs_fte_default_opts': (None, [C.POINTER(FteOpts)]),
@@ -292,6 +298,58 @@ def pack_cameras(K, D, R, t) -> np.ndarray:
     return cams
 
 
+def pack_cameras_standard(K, D, R, t) -> np.ndarray:
+    """(C,3,3), D, (C,3,3), (C,3[,1]) -> (C, 24) standard-model camera records (header:
+    ACS_CAMS_STANDARD). D holds OpenCV's (k1, k2, p1, p2[, k3[, k4, k5, k6]]) per camera: 4, 5
+    or 8 coefficients as (C, n), (C, n, 1) or (C, 1, n), zero-padded to 8. The 12- and
+    14-coefficient forms are taken only if their extra (thin-prism, tilt) terms are zero."""
+    K = np.asarray(K, np.float64).reshape(-1, 3, 3)
+    n = len(K)
+    D = np.asarray(D, np.float64).reshape(n, -1)
+    nd = D.shape[1]
+    if nd in (12, 14):
+        if np.any(D[:, 8:] != 0.0):
+            raise ValueError('pack_cameras_standard: the thin-prism (s1..s4) and tilt (tau_x, tau_y) coefficients '
+                             'of the 12- / 14-coefficient model are not supported (they must be zero)')
+        D, nd = D[:, :8], 8
+    if nd not in (4, 5, 8):
+        raise ValueError(f'pack_cameras_standard: {nd} distortion coefficients per camera (4, 5 or 8 expected)')
+    R = np.asarray(R, np.float64).reshape(n, 3, 3)
+    t = np.asarray(t, np.float64).reshape(n, 3)
+    cams = np.zeros((n, ACS_CAM_STRIDE_STD))
+    cams[:, 0] = K[:, 0, 0]
+    cams[:, 1] = K[:, 1, 1]
+    cams[:, 2] = K[:, 0, 2]
+    cams[:, 3] = K[:, 1, 2]
+    cams[:, 4:4 + nd] = D
+    cams[:, 12:21] = R.reshape(n, 9)
+    cams[:, 21:24] = t
+    return cams
+
+
+def _cams_flags(cams):
+    """Camera records as a contiguous (C, 20 | 24) float64 array and the flags bit of their
+    model, taken from the record width."""
+    cams = np.ascontiguousarray(cams, dtype=np.float64)
+    if cams.ndim != 2 or cams.shape[1] not in (ACS_CAM_STRIDE, ACS_CAM_STRIDE_STD):
+        raise ValueError(f'camera records of shape {cams.shape}: (C, {ACS_CAM_STRIDE}) fisheye (pack_cameras) or '
+                         f'(C, {ACS_CAM_STRIDE_STD}) standard (pack_cameras_standard) expected')
+    return cams, (ACS_CAMS_STANDARD if cams.shape[1] == ACS_CAM_STRIDE_STD else 0)
+
+
+def _std_flag(cams):
+    """ACS_CAMS_STANDARD for (C, 24) records, else 0: passed on by the bindings of the fisheye-only
+    entry points, so that the library refuses standard records by name instead of reading them
+    with the wrong stride."""
+    return ACS_CAMS_STANDARD if np.ndim(cams) == 2 and np.shape(cams)[1] == ACS_CAM_STRIDE_STD else 0
+
+
+def _model_flags(camera_model):
+    if camera_model not in CAMERA_MODELS:
+        raise ValueError(f"camera_model must be 'fisheye' or 'standard', not {camera_model!r}")
+    return ACS_CAMS_STANDARD if camera_model == 'standard' else 0
+
+
 class Context:
     """One HIP device + stream (acs_ctx). Methods take numpy arrays (host pointers)
     unless `device_ptrs=True`, in which case they take raw device addresses (ints)."""
@@ -332,25 +390,33 @@ class Context:
 
     # ---- a1 -------------------------------------------------------------------------
     def project(self, cams, pts, cam_idx=None, fte_form=False):
-        cams = _c64(cams)
+        """Projection through (C, 20) fisheye or (C, 24) standard records (the width selects)."""
+        cams, mf = _cams_flags(cams)
         pts = _c64(pts).reshape(-1, 3)
         n = len(pts)
         ci = None if cam_idx is None else np.ascontiguousarray(np.broadcast_to(cam_idx, (n,)), np.int32)
         out = np.empty((n, 2))
+        if mf:
+            if fte_form:
+                raise ValueError('project: fte_form is the FTE restatement of the fisheye model; standard records '
+                                 'have none')
+            self.check(self.lib.acs_project_standard(self.h, _ptr(cams), len(cams), _ptr(pts), _ptr(ci), n, _ptr(out),
+                                                     mf), 'acs_project_standard')
+            return out
         self.check(self.lib.acs_project_fisheye(self.h, _ptr(cams), len(cams), _ptr(pts), _ptr(ci), n,
                                                 int(bool(fte_form)), _ptr(out), 0), 'acs_project_fisheye')
         return out
 
     # ---- a2 -------------------------------------------------------------------------
     def sba_residuals(self, cams, uv, pt_idx, cam_idx, pts):
-        cams = _c64(cams)
+        cams, mf = _cams_flags(cams)
         uv = _c64(uv).reshape(-1, 2)
         pi = np.ascontiguousarray(pt_idx, np.int32)
         ci = np.ascontiguousarray(cam_idx, np.int32)
         pts = _c64(pts).reshape(-1, 3)
         out = np.empty(2 * len(uv))
         self.check(self.lib.acs_sba_residuals(self.h, _ptr(cams), len(cams), _ptr(uv), _ptr(pi), _ptr(ci), len(uv),
-                                              _ptr(pts), len(pts), _ptr(out), 0), 'acs_sba_residuals')
+                                              _ptr(pts), len(pts), _ptr(out), mf), 'acs_sba_residuals')
         return out
 
     # ---- a4 -------------------------------------------------------------------------
@@ -359,7 +425,7 @@ class Context:
         return SbaOpts(int(max_iters), 0, float(f_scale), float(ftol), float(xtol), float(gtol))
 
     def sba_points(self, cams, uv, pt_idx, cam_idx, pts0, opts=None, residuals=True):
-        cams = _c64(cams)
+        cams, mf = _cams_flags(cams)
         uv = _c64(uv).reshape(-1, 2)
         pi = np.ascontiguousarray(pt_idx, np.int32)
         ci = np.ascontiguousarray(cam_idx, np.int32)
@@ -369,7 +435,7 @@ class Context:
         rep = Report()
         opts = opts or self.sba_opts()
         self.check(self.lib.acs_sba_points(self.h, _ptr(cams), len(cams), _ptr(uv), _ptr(pi), _ptr(ci), len(uv),
-                                           _ptr(pts), len(pts), C.byref(opts), _ptr(rb), _ptr(ra), C.byref(rep), 0),
+                                           _ptr(pts), len(pts), C.byref(opts), _ptr(rb), _ptr(ra), C.byref(rep), mf),
                    'acs_sba_points')
         return pts, rb, ra, rep.as_dict()
 
@@ -378,17 +444,19 @@ class Context:
         context launch where both are legal (3..8 slots, no camera ids): 'auto', 'butterfly' or 'row'."""
         self.check(self.lib.acs_sba_set_lm_layout(self.h, SBA_LM_LAYOUTS[layout]), 'acs_sba_set_lm_layout')
 
-    def sba_lm_layout(self, n_slots, n_pts, cam_ids=False):
-        """acs_sba_lm_layout -> ('butterfly' | 'row', n_cu): what a solve of this size would launch under
-        the current setting, and the CU count the selection works with."""
+    def sba_lm_layout(self, n_slots, n_pts, cam_ids=False, camera_model='fisheye'):
+        """acs_sba_lm_layout[_flags] -> ('butterfly' | 'row', n_cu): what a solve of this size would
+        launch under the current setting, and the CU count the selection works with. The standard
+        model always reports 'butterfly' (it has no row instance)."""
         n_cu = C.c_int32(0)
-        rc = self.lib.acs_sba_lm_layout(self.h, int(n_slots), int(n_pts), int(bool(cam_ids)), C.byref(n_cu))
+        rc = self.lib.acs_sba_lm_layout_flags(self.h, int(n_slots), int(n_pts), int(bool(cam_ids)), C.byref(n_cu),
+                                              _model_flags(camera_model))
         if rc < 0:
             raise ValueError('acs_sba_lm_layout: bad arguments')
         return {v: k for k, v in SBA_LM_LAYOUTS.items()}[rc], int(n_cu.value)
 
     def sba_points_dense(self, cams, uv, mask, pts0, opts=None):
-        cams = _c64(cams)
+        cams, mf = _cams_flags(cams)
         C_ = len(cams)
         uv = _c64(uv).reshape(-1, C_, 2)
         mask = np.ascontiguousarray(mask, np.uint8).reshape(-1, C_)
@@ -396,25 +464,27 @@ class Context:
         rep = Report()
         opts = opts or self.sba_opts()
         self.check(self.lib.acs_sba_points_dense(self.h, _ptr(cams), C_, _ptr(uv), _ptr(mask), len(pts), _ptr(pts),
-                                                 C.byref(opts), C.byref(rep), 0), 'acs_sba_points_dense')
+                                                 C.byref(opts), C.byref(rep), mf), 'acs_sba_points_dense')
         return pts, rep.as_dict()
 
     def sba_points_dense_dev(self, cams_p, n_cams, uv_p, mask_p, n_pts, pts_p, opts=None, report=False,
-                             pts_in_p=None):
+                             pts_in_p=None, camera_model='fisheye'):
         """Device-pointer variant (inputs resident in HBM; asynchronous unless report).
         With `pts_in_p` the initial points are read from there and the solution written
-        to `pts_p` (acs_sba_points_dense_io); otherwise `pts_p` is in/out."""
+        to `pts_p` (acs_sba_points_dense_io); otherwise `pts_p` is in/out. `camera_model` says
+        what the records at `cams_p` are: 'fisheye' (20 doubles) or 'standard' (24)."""
+        flags = ACS_DEVICE_PTRS | _model_flags(camera_model)
         opts = opts or self.sba_opts()
         rep = Report() if report else None
         rp = C.byref(rep) if rep is not None else None
         if pts_in_p is None:
             rc = self.lib.acs_sba_points_dense(self.h, C.c_void_p(cams_p), n_cams, C.c_void_p(uv_p),
                                                C.c_void_p(mask_p), n_pts, C.c_void_p(pts_p), C.byref(opts), rp,
-                                               ACS_DEVICE_PTRS)
+                                               flags)
         else:
             rc = self.lib.acs_sba_points_dense_io(self.h, C.c_void_p(cams_p), n_cams, C.c_void_p(uv_p),
                                                   C.c_void_p(mask_p), n_pts, C.c_void_p(pts_in_p),
-                                                  C.c_void_p(pts_p), C.byref(opts), rp, ACS_DEVICE_PTRS)
+                                                  C.c_void_p(pts_p), C.byref(opts), rp, flags)
         self.check(rc, 'acs_sba_points_dense')
         return rep.as_dict() if rep is not None else None
 
@@ -439,7 +509,7 @@ class Context:
         opts = opts or self.sba_ext_opts()
         self.check(self.lib.acs_sba_extrinsics(self.h, _ptr(cams), len(cams), _ptr(uv), _ptr(pi), _ptr(ci), len(uv),
                                                _ptr(pts), len(pts), C.byref(opts), _ptr(rb), _ptr(ra),
-                                               C.byref(rep), 0), 'acs_sba_extrinsics')
+                                               C.byref(rep), _std_flag(cams)), 'acs_sba_extrinsics')
         return cams, pts, rb, ra, rep.as_dict()
 
     # ---- f2: EKF + RTS smoother ----------------------------------------------------------
@@ -468,7 +538,7 @@ class Context:
                                         _ptr(_c64(r_std_base)), _ptr(_c64(Q)), _ptr(_c64(P0)), _ptr(s0),
                                         ekf_numerics_mode(ref_numerics, jacobian), float(eps), _ptr(out['x_pred']), _ptr(out['x_est']),
                                         _ptr(out['x_smooth']), _ptr(out.get('P_est')), _ptr(out.get('P_smooth')),
-                                        _ptr(outl), 0), 'acs_ekf_run')
+                                        _ptr(outl), _std_flag(cams)), 'acs_ekf_run')
         out['outliers'] = outl
         if single:
             out = {k: v[0] for k, v in out.items()}
@@ -522,7 +592,7 @@ class Context:
             self.h, _ptr(ints), len(ints), _ptr(reals), len(reals), _ptr(cams), Cn, _ptr(meas), _ptr(lik), S, N, Lo,
             _ptr(emap), float(fps), float(thresh), float(max_pixel_err), _ptr(_c64(r_std_base)), _ptr(_c64(Q)),
             _ptr(_c64(P0)), C.byref(opts), C.byref(spec), ekf_numerics_mode(ref_numerics, jacobian), float(eps), _ptr(pts), _ptr(xe),
-            _ptr(xs), _ptr(outl), C.byref(rep), 0), 'acs_sba_ekf_pipeline')
+            _ptr(xs), _ptr(outl), C.byref(rep), _std_flag(cams)), 'acs_sba_ekf_pipeline')
         return dict(pts=pts, x_est=xe, x_smooth=xs, outliers=outl, sba=rep.as_dict())
 
     def sba_ekf_pipeline_dev(self, table, obs_markers, cams_p, n_cams, meas_p, lik_p, S, N, fps, thresh,
@@ -613,7 +683,7 @@ class Context:
         self.check(self.lib.acs_fte_solve(self.h, _ptr(ints), len(ints), _ptr(reals), len(reals), _ptr(cams), Cn,
                                           _ptr(meas), _ptr(w), N, int(bool(shutter_delay)), float(Ts), _ptr(qinv),
                                           int(sd_mode), int(intermode), _ptr(X), _ptr(tau), C.byref(opts),
-                                          C.byref(rep), 0), 'acs_fte_solve')
+                                          C.byref(rep), _std_flag(cams)), 'acs_fte_solve')
         return X, tau, rep.as_dict()
 
     def fte_solve_dev(self, table_ints_p, n_ints, table_reals_p, n_reals, cams_p, n_cams, meas_p, w_p, N,
@@ -644,7 +714,7 @@ class Context:
         self.check(self.lib.acs_fte_eval(self.h, _ptr(ints), len(ints), _ptr(reals), len(reals), _ptr(cams), Cn,
                                          _ptr(meas), _ptr(w), N, int(bool(shutter_delay)), float(Ts), _ptr(qinv),
                                          int(sd_mode), int(intermode), _ptr(X), _ptr(tau), _ptr(cost), _ptr(grad),
-                                         _ptr(H), 0),
+                                         _ptr(H), _std_flag(cams)),
                    'acs_fte_eval')
         return cost, grad, H
 
@@ -666,7 +736,8 @@ class Context:
         self.check(self.lib.acs_fte_covariance(self.h, _ptr(ints), len(ints), _ptr(reals), len(reals), _ptr(cams), Cn,
                                                _ptr(meas), _ptr(w), N, int(bool(shutter_delay)), float(Ts),
                                                _ptr(qinv), int(sd_mode), int(intermode), _ptr(X), _ptr(tau),
-                                               _ptr(x_cov), _ptr(tau_cov), _ptr(marker_cov), C.byref(rep), 0),
+                                               _ptr(x_cov), _ptr(tau_cov), _ptr(marker_cov), C.byref(rep),
+                                               _std_flag(cams)),
                    'acs_fte_covariance')
         return dict(x_cov=x_cov, tau_cov=tau_cov, marker_cov=marker_cov, n_bad_pivots=int(rep.n_bad_pivots),
                     n_tau_free=int(rep.n_tau_free), var_min=float(rep.var_min), var_max=float(rep.var_max))
@@ -705,13 +776,13 @@ class Context:
         self.check(self.lib.acs_fte_debug_blocks(self.h, _ptr(ints), len(ints), _ptr(reals), len(reals), _ptr(cams), Cn,
                                                  _ptr(meas), _ptr(w), N, int(bool(shutter_delay)), float(Ts),
                                                  _ptr(qinv), 0, int(intermode), _ptr(X), _ptr(tau), float(lam),
-                                                 int(levels), _ptr(D), dims, 0), 'acs_fte_debug_blocks')
+                                                 int(levels), _ptr(D), dims, _std_flag(cams)), 'acs_fte_debug_blocks')
         assert dims[0] == nblk and dims[1] == BP, (list(dims), nblk, BP)
         return D, int(dims[2])
 
     # ---- triangulation -------------------------------------------------
     def triangulate_pairs(self, cams, uv_a, uv_b, cam_a, cam_b):
-        cams = _c64(cams)
+        cams, mf = _cams_flags(cams)
         uv_a = _c64(uv_a).reshape(-1, 2)
         uv_b = _c64(uv_b).reshape(-1, 2)
         n = len(uv_a)
@@ -719,11 +790,11 @@ class Context:
         cb = np.ascontiguousarray(np.broadcast_to(cam_b, (n,)), np.int32)
         out = np.empty((n, 3))
         self.check(self.lib.acs_triangulate_pairs(self.h, _ptr(cams), len(cams), _ptr(uv_a), _ptr(uv_b), _ptr(ca),
-                                                  _ptr(cb), n, _ptr(out), 0), 'acs_triangulate_pairs')
+                                                  _ptr(cb), n, _ptr(out), mf), 'acs_triangulate_pairs')
         return out
 
     def triangulate_dense(self, cams, uv, mask):
-        cams = _c64(cams)
+        cams, mf = _cams_flags(cams)
         C_ = len(cams)
         uv = _c64(np.nan_to_num(uv)).reshape(-1, C_, 2)
         mask = np.ascontiguousarray(mask, np.uint8).reshape(-1, C_)
@@ -731,7 +802,7 @@ class Context:
         out = np.empty((n, 3))
         cnt = np.empty(n, np.int32)
         self.check(self.lib.acs_triangulate_dense(self.h, _ptr(cams), C_, _ptr(uv), _ptr(mask), n, _ptr(out),
-                                                  _ptr(cnt), 0), 'acs_triangulate_dense')
+                                                  _ptr(cnt), mf), 'acs_triangulate_dense')
         return out, cnt
 
 

@@ -1,7 +1,8 @@
 """`core.tri` (src/core/tri.py:27-64): filter by likelihood and frame window, pairwise
 fisheye triangulation of adjacent cameras on the GPU (`lib.utils.get_pairwise_3d_points_
 from_df` -> `acs_triangulate_pairs`), reprojection table, tri.pickle (+ .mat) and the
-cam*_tri reprojections (`lib.app.save_tri`).
+cam*_tri reprojections (`lib.app.save_tri`). `camera_model='standard'` triangulates, measures
+and reprojects through the standard (pinhole) model instead.
 
 The reference's `save_error_dists` (src/core/metrics.py:26-93, PDF histograms) is
 reporting, out of scope; the error tables it would plot are kept
@@ -12,11 +13,14 @@ from typing import Dict
 
 import numpy as np
 
-from ..lib import app, metric, misc, utils
+from ..lib import app, calib, metric, misc, utils
 
 
 def tri(DATA_DIR, points_2d_df, start_frame, end_frame, dlc_thresh, camera_params, scene_fpath,
-        params: Dict = {}) -> str:
+        params: Dict = {}, camera_model: str = 'fisheye') -> str:
+    if camera_model not in ('fisheye', 'standard'):
+        raise ValueError(f"camera_model must be 'fisheye' or 'standard', not {camera_model!r}")
+    standard = camera_model == 'standard'
     OUT_DIR = os.path.join(DATA_DIR, 'tri')
     os.makedirs(OUT_DIR, exist_ok=True)
     markers = misc.get_markers(mode='all')
@@ -27,10 +31,15 @@ def tri(DATA_DIR, points_2d_df, start_frame, end_frame, dlc_thresh, camera_param
         json.dump(params, f)
     points_2d_df = points_2d_df.query(f'likelihood > {dlc_thresh}')
     points_2d_df = points_2d_df[points_2d_df['frame'].between(start_frame, end_frame)]
-    points_3d_df = utils.get_pairwise_3d_points_from_df(points_2d_df, k_arr, np.asarray(d_arr).reshape((-1, 4)),
-                                                        r_arr, t_arr)
+    if standard:
+        points_3d_df = utils.get_pairwise_3d_points_from_df(points_2d_df, k_arr, d_arr, r_arr, t_arr,
+                                                            calib.triangulate_points)
+    else:
+        points_3d_df = utils.get_pairwise_3d_points_from_df(points_2d_df, k_arr, np.asarray(d_arr).reshape((-1, 4)),
+                                                            r_arr, t_arr)
     points_3d_df['point_index'] = points_3d_df.index
-    pix_errors = metric.residual_error(points_2d_df, points_3d_df, markers, camera_params)
+    project_func = calib.project_points if standard else None
+    pix_errors = metric.residual_error(points_2d_df, points_3d_df, markers, camera_params, project_func)
     positions = np.full((end_frame - start_frame + 1, len(markers), 3), np.nan)
     mi = {m: i for i, m in enumerate(markers)}
     keep = points_3d_df['marker'].isin(mi)
@@ -38,4 +47,5 @@ def tri(DATA_DIR, points_2d_df, start_frame, end_frame, dlc_thresh, camera_param
     fr = sel['frame'].to_numpy().astype(int) - start_frame
     mk = np.array([mi[m] for m in sel['marker']], dtype=int)
     positions[fr, mk] = sel[['x', 'y', 'z']].to_numpy(np.float64)
-    return app.save_tri(positions, OUT_DIR, scene_fpath, markers, start_frame, pix_errors, save_videos=True)
+    return app.save_tri(positions, OUT_DIR, scene_fpath, markers, start_frame, pix_errors, save_videos=True,
+                        project_func=project_func)

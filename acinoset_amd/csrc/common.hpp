@@ -1,4 +1,4 @@
-// common.hpp — context, device workspace, error plumbing and the fisheye camera model
+// common.hpp — context, device workspace, error plumbing and the two camera models
 // shared by every translation unit of libacinoset_hip.so (gfx950 only).
 #pragma once
 
@@ -119,10 +119,11 @@ int acs_obs_to_slots(acs_ctx* ctx, const double* duv, const int32_t* dpi, const 
 // report, waits for it (else asynchronous on the context stream).
 int acs_sba_dense_enqueue(acs_ctx* ctx, const double* dcams, int C, const double2* duv, const uint8_t* dmask,
                           int64_t n_pts, const double* dpts_in, double* dpts_out, const acs_sba_opts* opts,
-                          acs_report* report);
-// Pairwise fisheye triangulation of the dense slots (tri.hip): mean over adjacent pairs.
+                          acs_report* report, int model = 0);
+// Pairwise triangulation of the dense slots (tri.hip): mean over adjacent pairs.
+// model (both): 0 = fisheye records (the default), 1 = standard records (ACS_MODEL_*, below).
 int acs_tri_dense_enqueue(acs_ctx* ctx, const double* dcams, int C, const double* duv, const uint8_t* dmask,
-                          int64_t n_pts, double* dout, int32_t* dcnt);
+                          int64_t n_pts, double* dout, int32_t* dcnt, int model = 0);
 // EKF + RTS smoother (ekf.hip) on device buffers.
 struct EkfIo {
   const int* I = nullptr;
@@ -257,6 +258,127 @@ __device__ __forceinline__ void fisheye_uvj(const double* __restrict__ c, double
     J[j] = fma(ua, A, ub * B);
     J[3 + j] = fma(va, A, vb * B);
   }
+}
+
+// ------------------------------------------------------------------------------------
+// Standard (pinhole) camera model (cv::projectPoints with up to 8 coefficients;
+// src/lib/calib.py:65-67). Camera record layout:
+// [fx fy cx cy k1 k2 p1 p2 k3 k4 k5 k6 R00..R22 t0 t1 t2] (ACS_CAM_STRIDE_STD = 24 doubles;
+// a shorter coefficient vector is zero-padded by the packer). With a = Y0/Y2, b = Y1/Y2,
+// r2 = a^2 + b^2 and cd = (1 + k1 r2 + k2 r2^2 + k3 r2^3) / (1 + k4 r2 + k5 r2^2 + k6 r2^3):
+//   xd = a cd + 2 p1 a b + p2 (r2 + 2 a^2),  yd = b cd + p1 (r2 + 2 b^2) + 2 p2 a b,
+//   u = fx xd + cx, v = fy yd + cy.
+// No guard: a point behind the camera projects by the same formula, as OpenCV's does. The null
+// record (all zeros, t2 = 1) gives u = v = 0 and a zero Jacobian exactly (fx = fy = 0).
+// ------------------------------------------------------------------------------------
+enum : int { ACS_MODEL_FISHEYE = 0, ACS_MODEL_STANDARD = 1 };
+template <int MODEL>
+struct CamRec {
+  static constexpr int stride = MODEL == ACS_MODEL_STANDARD ? ACS_CAM_STRIDE_STD : ACS_CAM_STRIDE;
+  static constexpr int R = stride - 12;  // first entry of the rotation; t follows it
+};
+static inline int acs_cam_stride(int model) { return model == ACS_MODEL_STANDARD ? ACS_CAM_STRIDE_STD : ACS_CAM_STRIDE; }
+static inline int acs_flags_model(uint32_t flags) {
+  return (flags & ACS_CAMS_STANDARD) ? ACS_MODEL_STANDARD : ACS_MODEL_FISHEYE;
+}
+// every entry point whose cameras must be fisheye records starts with this
+#define ACS_FISHEYE_ONLY(ctx, flags, fn) \
+  ACS_CHECK(ctx, !((flags) & ACS_CAMS_STANDARD), fn ": the standard camera model (ACS_CAMS_STANDARD) is not supported here")
+
+// the distorted normalised point and, with JAC, its partials (xa = dxd/da, xb = dxd/db = dyd/da,
+// yb = dyd/db); c' = d cd / d r2 = (num' - cd den') / den
+template <bool JAC>
+__device__ __forceinline__ void standard_distort(const double* __restrict__ c, double a, double b, double& xd,
+                                                 double& yd, double& xa, double& xb, double& yb) {
+  const double k1 = c[4], k2 = c[5], p1 = c[6], p2 = c[7], k3 = c[8], k4 = c[9], k5 = c[10], k6 = c[11];
+  const double aa = a * a, bb = b * b, ab = a * b;
+  const double r2 = aa + bb;
+  const double num = fma(r2, fma(r2, fma(r2, k3, k2), k1), 1.0);
+  const double den = fma(r2, fma(r2, fma(r2, k6, k5), k4), 1.0);
+  const double id = rcp_nr(den);
+  const double cd = num * id;
+  xd = fma(a, cd, fma(2.0 * p1, ab, p2 * (r2 + 2.0 * aa)));
+  yd = fma(b, cd, fma(p1, r2 + 2.0 * bb, 2.0 * p2 * ab));
+  if (JAC) {
+    const double dnum = fma(r2, fma(r2, 3.0 * k3, 2.0 * k2), k1);
+    const double dden = fma(r2, fma(r2, 3.0 * k6, 2.0 * k5), k4);
+    const double cp2 = 2.0 * (dnum - cd * dden) * id;  // 2 c'
+    xa = fma(aa, cp2, cd) + fma(2.0 * p1, b, 6.0 * p2 * a);
+    xb = fma(ab, cp2, 2.0 * fma(p1, a, p2 * b));
+    yb = fma(bb, cp2, cd) + fma(6.0 * p1, b, 2.0 * p2 * a);
+  }
+}
+
+// fills the same ProjOut as fisheye_project
+template <bool JAC>
+__device__ __forceinline__ void standard_project(const double* __restrict__ c, double X0, double X1, double X2,
+                                                 ProjOut& o) {
+  const double Y0 = fma(c[12], X0, fma(c[13], X1, fma(c[14], X2, c[21])));
+  const double Y1 = fma(c[15], X0, fma(c[16], X1, fma(c[17], X2, c[22])));
+  const double Y2 = fma(c[18], X0, fma(c[19], X1, fma(c[20], X2, c[23])));
+  const double iz = rcp_nr(Y2);
+  const double a = Y0 * iz;
+  const double b = Y1 * iz;
+  double xd, yd, xa = 0.0, xb = 0.0, yb = 0.0;
+  standard_distort<JAC>(c, a, b, xd, yd, xa, xb, yb);
+  o.u = c[0] * xd + c[2];
+  o.v = c[1] * yd + c[3];
+  if (JAC) {
+    const double duda = c[0] * xa, dudb = c[0] * xb, dvda = c[1] * xb, dvdb = c[1] * yb;
+    const double u0 = duda * iz, u1 = dudb * iz, u2 = -(duda * a + dudb * b) * iz;
+    const double v0 = dvda * iz, v1 = dvdb * iz, v2 = -(dvda * a + dvdb * b) * iz;
+    o.JY[0] = u0;
+    o.JY[1] = u1;
+    o.JY[2] = u2;
+    o.JY[3] = v0;
+    o.JY[4] = v1;
+    o.JY[5] = v2;
+    o.Y[0] = Y0;
+    o.Y[1] = Y1;
+    o.Y[2] = Y2;
+    o.J[0] = u0 * c[12] + u1 * c[15] + u2 * c[18];
+    o.J[1] = u0 * c[13] + u1 * c[16] + u2 * c[19];
+    o.J[2] = u0 * c[14] + u1 * c[17] + u2 * c[20];
+    o.J[3] = v0 * c[12] + v1 * c[15] + v2 * c[18];
+    o.J[4] = v0 * c[13] + v1 * c[16] + v2 * c[19];
+    o.J[5] = v0 * c[14] + v1 * c[17] + v2 * c[20];
+  }
+}
+
+// u, v and d(u, v)/dX for the points-only SBA LM (k_sba_lm), the camera-frame Jacobian folded
+// into R's rows exactly as in fisheye_uvj: A = R_0 - a R_2, B = R_1 - b R_2,
+// J_u = iz (du/da A + du/db B). Two reciprocals (1/Y2, 1/den), no atan and no rsq.
+__device__ __forceinline__ void standard_uvj(const double* __restrict__ c, double X0, double X1, double X2, double& u,
+                                             double& v, double* J) {
+  const double Y0 = fma(c[12], X0, fma(c[13], X1, fma(c[14], X2, c[21])));
+  const double Y1 = fma(c[15], X0, fma(c[16], X1, fma(c[17], X2, c[22])));
+  const double Y2 = fma(c[18], X0, fma(c[19], X1, fma(c[20], X2, c[23])));
+  const double iz = rcp_nr(Y2);
+  const double a = Y0 * iz;
+  const double b = Y1 * iz;
+  double xd, yd, xa, xb, yb;
+  standard_distort<true>(c, a, b, xd, yd, xa, xb, yb);
+  u = c[0] * xd + c[2];
+  v = c[1] * yd + c[3];
+  const double fu = c[0] * iz, fv = c[1] * iz;
+  const double ua = fu * xa, ub = fu * xb;  // iz du/da, iz du/db
+  const double va = fv * xb, vb = fv * yb;  // iz dv/da, iz dv/db
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const double A = fma(-a, c[18 + j], c[12 + j]), B = fma(-b, c[18 + j], c[15 + j]);
+    J[j] = fma(ua, A, ub * B);
+    J[3 + j] = fma(va, A, vb * B);
+  }
+}
+
+// the model's projection by a template argument (the elementwise kernels and k_sba_lm)
+template <int MODEL, bool JAC>
+__device__ __forceinline__ void model_project(const double* __restrict__ c, double X0, double X1, double X2,
+                                              ProjOut& o) {
+  if constexpr (MODEL == ACS_MODEL_STANDARD)
+    standard_project<JAC>(c, X0, X1, X2, o);
+  else
+    fisheye_project<JAC>(c, X0, X1, X2, o);
 }
 
 // ------------------------------------------------------------------------------------

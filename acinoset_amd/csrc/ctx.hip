@@ -174,6 +174,7 @@ int acs_ctx_sync(acs_ctx* ctx) {
 // ------------------------------------------------------------------------------------
 // a1: projection, a2: residual vector, a9: loss
 // ------------------------------------------------------------------------------------
+template <int MODEL>
 __global__ __launch_bounds__(256) void k_project(const double* __restrict__ cams, int n_cams,
                                                  const double* __restrict__ pts,
                                                  const int32_t* __restrict__ cam_idx, int64_t n,
@@ -186,7 +187,9 @@ __global__ __launch_bounds__(256) void k_project(const double* __restrict__ cams
     return;
   }
   ProjOut o;
-  if (fte_form)
+  if constexpr (MODEL == ACS_MODEL_STANDARD)
+    standard_project<false>(cams + c * ACS_CAM_STRIDE_STD, pts[3 * i], pts[3 * i + 1], pts[3 * i + 2], o);
+  else if (fte_form)
     fisheye_project<false, true>(cams + c * ACS_CAM_STRIDE, pts[3 * i], pts[3 * i + 1], pts[3 * i + 2], o);
   else
     fisheye_project<false, false>(cams + c * ACS_CAM_STRIDE, pts[3 * i], pts[3 * i + 1], pts[3 * i + 2], o);
@@ -194,6 +197,7 @@ __global__ __launch_bounds__(256) void k_project(const double* __restrict__ cams
   uv[2 * i + 1] = o.v;
 }
 
+template <int MODEL>
 __global__ __launch_bounds__(256) void k_residuals(const double* __restrict__ cams, int n_cams,
                                                    const double* __restrict__ uvobs,
                                                    const int32_t* __restrict__ pt_idx,
@@ -209,7 +213,7 @@ __global__ __launch_bounds__(256) void k_residuals(const double* __restrict__ ca
     return;
   }
   ProjOut o;
-  fisheye_project<false>(cams + c * ACS_CAM_STRIDE, pts[3 * p], pts[3 * p + 1], pts[3 * p + 2], o);
+  model_project<MODEL, false>(cams + c * CamRec<MODEL>::stride, pts[3 * p], pts[3 * p + 1], pts[3 * p + 2], o);
   res[2 * i] = o.u - uvobs[2 * i];
   res[2 * i + 1] = o.v - uvobs[2 * i + 1];
 }
@@ -223,27 +227,47 @@ __global__ __launch_bounds__(256) void k_loss(const double* __restrict__ e, int6
   if (dout) dout[i] = l.d1;
 }
 
+// the two projection entry points: model 0 = fisheye records, 1 = standard records
+static int project_any(acs_ctx* ctx, int model, const char* fn, const double* cams, int32_t n_cams,
+                       const double* pts, const int32_t* cam_idx, int64_t n, int32_t fte_form, double* uv_out,
+                       uint32_t flags) {
+  ACS_CHECK(ctx, n >= 0 && n_cams > 0, "%s: n=%lld n_cams=%d", fn, (long long)n, n_cams);
+  if (n == 0) return ACS_OK;
+  void *dc, *dp, *di = nullptr;
+  int rc;
+  if ((rc = acs_stage_in(ctx, WS_CAMS, cams, sizeof(double) * acs_cam_stride(model) * n_cams, flags, &dc))) return rc;
+  if ((rc = acs_stage_in(ctx, WS_PTS, pts, sizeof(double) * 3 * n, flags, &dp))) return rc;
+  if (cam_idx && (rc = acs_stage_in(ctx, WS_CAMIDX, cam_idx, sizeof(int32_t) * n, flags, &di))) return rc;
+  double* duv = (double*)acs_out_buf(ctx, WS_OUT0, uv_out, sizeof(double) * 2 * n, flags);
+  if (!duv) return ACS_E_NOMEM;
+  if (model == ACS_MODEL_STANDARD)
+    hipLaunchKernelGGL(k_project<ACS_MODEL_STANDARD>, dim3(acs_grid(n, 256)), dim3(256), 0, ctx->stream,
+                       (const double*)dc, n_cams, (const double*)dp, (const int32_t*)di, n, 0, duv);
+  else
+    hipLaunchKernelGGL(k_project<ACS_MODEL_FISHEYE>, dim3(acs_grid(n, 256)), dim3(256), 0, ctx->stream,
+                       (const double*)dc, n_cams, (const double*)dp, (const int32_t*)di, n, fte_form, duv);
+  ACS_HIP(ctx, hipGetLastError());
+  if ((rc = acs_stage_out(ctx, uv_out, duv, sizeof(double) * 2 * n, flags))) return rc;
+  if (!(flags & ACS_DEVICE_PTRS)) ACS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return ACS_OK;
+}
+
 extern "C" {
 
 int acs_project_fisheye(acs_ctx* ctx, const double* cams, int32_t n_cams, const double* pts,
                         const int32_t* cam_idx, int64_t n, int32_t fte_form, double* uv_out,
                         uint32_t flags) {
   ACS_DEVICE_GUARD(ctx);
-  ACS_CHECK(ctx, n >= 0 && n_cams > 0, "acs_project_fisheye: n=%lld n_cams=%d", (long long)n, n_cams);
-  if (n == 0) return ACS_OK;
-  void *dc, *dp, *di = nullptr;
-  int rc;
-  if ((rc = acs_stage_in(ctx, WS_CAMS, cams, sizeof(double) * ACS_CAM_STRIDE * n_cams, flags, &dc))) return rc;
-  if ((rc = acs_stage_in(ctx, WS_PTS, pts, sizeof(double) * 3 * n, flags, &dp))) return rc;
-  if (cam_idx && (rc = acs_stage_in(ctx, WS_CAMIDX, cam_idx, sizeof(int32_t) * n, flags, &di))) return rc;
-  double* duv = (double*)acs_out_buf(ctx, WS_OUT0, uv_out, sizeof(double) * 2 * n, flags);
-  if (!duv) return ACS_E_NOMEM;
-  hipLaunchKernelGGL(k_project, dim3(acs_grid(n, 256)), dim3(256), 0, ctx->stream, (const double*)dc, n_cams,
-                     (const double*)dp, (const int32_t*)di, n, fte_form, duv);
-  ACS_HIP(ctx, hipGetLastError());
-  if ((rc = acs_stage_out(ctx, uv_out, duv, sizeof(double) * 2 * n, flags))) return rc;
-  if (!(flags & ACS_DEVICE_PTRS)) ACS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return ACS_OK;
+  ACS_FISHEYE_ONLY(ctx, flags, "acs_project_fisheye");
+  return project_any(ctx, ACS_MODEL_FISHEYE, "acs_project_fisheye", cams, n_cams, pts, cam_idx, n, fte_form, uv_out,
+                     flags);
+}
+
+int acs_project_standard(acs_ctx* ctx, const double* cams, int32_t n_cams, const double* pts,
+                         const int32_t* cam_idx, int64_t n, double* uv_out, uint32_t flags) {
+  ACS_DEVICE_GUARD(ctx);
+  return project_any(ctx, ACS_MODEL_STANDARD, "acs_project_standard", cams, n_cams, pts, cam_idx, n, 0, uv_out,
+                     flags);
 }
 
 int acs_sba_residuals(acs_ctx* ctx, const double* cams, int32_t n_cams, const double* uv,
@@ -254,16 +278,22 @@ int acs_sba_residuals(acs_ctx* ctx, const double* cams, int32_t n_cams, const do
   if (n_obs == 0) return ACS_OK;
   void *dc, *duv, *dpi, *dci, *dp;
   int rc;
-  if ((rc = acs_stage_in(ctx, WS_CAMS, cams, sizeof(double) * ACS_CAM_STRIDE * n_cams, flags, &dc))) return rc;
+  const int model = acs_flags_model(flags);
+  if ((rc = acs_stage_in(ctx, WS_CAMS, cams, sizeof(double) * acs_cam_stride(model) * n_cams, flags, &dc))) return rc;
   if ((rc = acs_stage_in(ctx, WS_UV, uv, sizeof(double) * 2 * n_obs, flags, &duv))) return rc;
   if ((rc = acs_stage_in(ctx, WS_PTIDX, pt_idx, sizeof(int32_t) * n_obs, flags, &dpi))) return rc;
   if ((rc = acs_stage_in(ctx, WS_CAMIDX, cam_idx, sizeof(int32_t) * n_obs, flags, &dci))) return rc;
   if ((rc = acs_stage_in(ctx, WS_PTS, pts, sizeof(double) * 3 * n_pts, flags, &dp))) return rc;
   double* dr = (double*)acs_out_buf(ctx, WS_OUT0, resid_out, sizeof(double) * 2 * n_obs, flags);
   if (!dr) return ACS_E_NOMEM;
-  hipLaunchKernelGGL(k_residuals, dim3(acs_grid(n_obs, 256)), dim3(256), 0, ctx->stream, (const double*)dc,
-                     n_cams, (const double*)duv, (const int32_t*)dpi, (const int32_t*)dci, n_obs,
-                     (const double*)dp, n_pts, dr);
+  if (model == ACS_MODEL_STANDARD)
+    hipLaunchKernelGGL(k_residuals<ACS_MODEL_STANDARD>, dim3(acs_grid(n_obs, 256)), dim3(256), 0, ctx->stream,
+                       (const double*)dc, n_cams, (const double*)duv, (const int32_t*)dpi, (const int32_t*)dci, n_obs,
+                       (const double*)dp, n_pts, dr);
+  else
+    hipLaunchKernelGGL(k_residuals<ACS_MODEL_FISHEYE>, dim3(acs_grid(n_obs, 256)), dim3(256), 0, ctx->stream,
+                       (const double*)dc, n_cams, (const double*)duv, (const int32_t*)dpi, (const int32_t*)dci, n_obs,
+                       (const double*)dp, n_pts, dr);
   ACS_HIP(ctx, hipGetLastError());
   if ((rc = acs_stage_out(ctx, resid_out, dr, sizeof(double) * 2 * n_obs, flags))) return rc;
   if (!(flags & ACS_DEVICE_PTRS)) ACS_HIP(ctx, hipStreamSynchronize(ctx->stream));

@@ -2580,6 +2580,7 @@ int acs_ekf_run(acs_ctx* ctx, const int32_t* skel_ints, int64_t n_ints, const do
                 double* x_pred, double* x_est, double* x_smooth, double* P_est, double* P_smooth,
                 int64_t* outliers, uint32_t flags) {
   ACS_DEVICE_GUARD(ctx);
+  ACS_FISHEYE_ONLY(ctx, flags, "acs_ekf_run");
   int hdr[FK_HDR];
   if (flags & ACS_DEVICE_PTRS)
     ACS_HIP(ctx, hipMemcpy(hdr, skel_ints, sizeof(hdr), hipMemcpyDeviceToHost));

@@ -3850,6 +3850,7 @@ int acs_fte_solve(acs_ctx* ctx, const int32_t* skel_ints, int64_t n_ints, const 
                   int32_t shutter_delay, double Ts, const double* qinv, int32_t sd_mode, int32_t intermode, double* X,
                   double* tau, const acs_fte_opts* opts, acs_fte_report* report, uint32_t flags) {
   ACS_DEVICE_GUARD(ctx);
+  ACS_FISHEYE_ONLY(ctx, flags, "acs_fte_solve");
   acs_fte_opts op;
   acs_fte_default_opts(&op);
   if (opts) op = *opts;
@@ -3941,6 +3942,7 @@ int acs_fte_eval(acs_ctx* ctx, const int32_t* skel_ints, int64_t n_ints, const d
                  int32_t shutter_delay, double Ts, const double* qinv, int32_t sd_mode, int32_t intermode,
                  const double* X, const double* tau, double* cost3, double* grad, double* H, uint32_t flags) {
   ACS_DEVICE_GUARD(ctx);
+  ACS_FISHEYE_ONLY(ctx, flags, "acs_fte_eval");
   ACS_CHECK(ctx, !(flags & ACS_DEVICE_PTRS), "acs_fte_eval takes host pointers");
   FteSetup S;
   int rc;
@@ -4046,6 +4048,7 @@ int acs_fte_debug_blocks(acs_ctx* ctx, const int32_t* skel_ints, int64_t n_ints,
                          int32_t intermode, const double* X, const double* tau, double lam, int32_t levels,
                          double* D_out, int64_t* dims, uint32_t flags) {
   ACS_DEVICE_GUARD(ctx);
+  ACS_FISHEYE_ONLY(ctx, flags, "acs_fte_debug_blocks");
   ACS_CHECK(ctx, D_out && levels >= 0, "acs_fte_debug_blocks: null D_out or levels < 0");
   ACS_CHECK(ctx, !(shutter_delay && sd_mode == 1), "acs_fte_debug_blocks: constant or no shutter delay only");
   FteSetup S;
@@ -4138,6 +4141,7 @@ int acs_fte_dist_create(acs_ctx* ctx, const int32_t* skel_ints, int64_t n_ints, 
                         int32_t intermode, const double* X, const double* tau, const acs_fte_opts* opts, int32_t rank,
                         int32_t world, acs_fte_dist** out, int64_t* payload_sizes, uint32_t flags) {
   ACS_DEVICE_GUARD(ctx);
+  ACS_FISHEYE_ONLY(ctx, flags, "acs_fte_dist_create");
   acs_fte_opts op;
   acs_fte_default_opts(&op);
   if (opts) op = *opts;

@@ -505,6 +505,7 @@ extern "C" int acs_fte_covariance(acs_ctx* ctx, const int32_t* skel_ints, int64_
                                   const double* tau, double* cov_x, double* cov_tau, double* cov_marker,
                                   acs_fte_cov_report* report, uint32_t flags) {
   ACS_DEVICE_GUARD(ctx);
+  ACS_FISHEYE_ONLY(ctx, flags, "acs_fte_covariance");
   ACS_CHECK(ctx, X && cov_x, "acs_fte_covariance: null X or cov_x");
   ACS_CHECK(ctx, !(shutter_delay && sd_mode == 1),
             "acs_fte_covariance: shutter_delay_mode 'variable' is not supported (the per-frame delays are "

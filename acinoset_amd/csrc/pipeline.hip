@@ -162,6 +162,7 @@ int acs_sba_ekf_pipeline(acs_ctx* ctx, const int32_t* skel_ints, int64_t n_ints,
                          double* x_est, double* x_smooth, int64_t* outliers, acs_report* sba_report,
                          uint32_t flags) {
   ACS_DEVICE_GUARD(ctx);
+  ACS_FISHEYE_ONLY(ctx, flags, "acs_sba_ekf_pipeline");
   ACS_CHECK(ctx, skel_ints && skel_reals && ekf_markers && init, "pipeline: null descriptor");
   ACS_CHECK(ctx, n_ints >= FK_HDR, "pipeline: skeleton table");
   const int* hdr = skel_ints;  // host descriptor

@@ -81,7 +81,10 @@ struct SbaParams {
 // ROW (0, or the number of lane pairs 2..4): the row-broadcast sums of common.hpp in place of the
 // butterfly. G = 16 (one point per DPP row), S = 1, no camera ids, HOIST only: the instance for
 // latency-bound grids, where a wave of 4 points instead of 8 costs nothing (run_lm).
-template <int G, int S, bool CAMID, bool HOIST, int ROW = 0>
+// MODEL (ACS_MODEL_*): the projection, the record stride and the place of the null record's 1.0.
+// The standard model has the LDS-staged butterfly instances only: the HOIST and ROW instances'
+// null-record moves are written out for the 20 doubles of a fisheye record.
+template <int G, int S, bool CAMID, bool HOIST, int ROW = 0, int MODEL = ACS_MODEL_FISHEYE>
 __global__ __launch_bounds__(256) void k_sba_lm(const double2* __restrict__ uv,
                                                 const uint8_t* __restrict__ mask, int64_t n_pts,
                                                 const double* pts_in, const double* __restrict__ cams,
@@ -91,6 +94,8 @@ __global__ __launch_bounds__(256) void k_sba_lm(const double2* __restrict__ uv,
                                                 double* __restrict__ cost0, double* __restrict__ cost1,
                                                 int* __restrict__ stat) {
   static_assert(ROW == 0 || (G == 16 && S == 1 && !CAMID && HOIST), "ROW: 16-lane rows, one slot per lane, hoisted records");
+  static_assert(MODEL == 0 || (!HOIST && ROW == 0), "standard model: LDS-staged butterfly instances only");
+  constexpr int CS = CamRec<MODEL>::stride;
   extern __shared__ double s_cam[];
   // every kernel argument the address computations need, requested before the first scalar
   // wait: left alone, the compiler loads each where the first branch that uses it begins,
@@ -139,8 +144,8 @@ __global__ __launch_bounds__(256) void k_sba_lm(const double2* __restrict__ uv,
     for (int i = 0; i < ACS_CAM_STRIDE; ++i) cr[0][i] = cg[i];
     if (!live) return;  // whole group leaves together
   } else {
-    for (int i = threadIdx.x; i < C * ACS_CAM_STRIDE; i += blockDim.x) s_cam[i] = cams[i];
-    if (threadIdx.x < ACS_CAM_STRIDE) s_cam[C * ACS_CAM_STRIDE + threadIdx.x] = threadIdx.x == 19 ? 1.0 : 0.0;
+    for (int i = threadIdx.x; i < C * CS; i += blockDim.x) s_cam[i] = cams[i];
+    if (threadIdx.x < CS) s_cam[C * CS + threadIdx.x] = threadIdx.x == CS - 1 ? 1.0 : 0.0;
     __syncthreads();
     if (!live) return;  // whole group leaves together
   }
@@ -156,7 +161,7 @@ __global__ __launch_bounds__(256) void k_sba_lm(const double2* __restrict__ uv,
     ok[s] = slot < K && mk[s] && cam < C;
     ou[s] = ok[s] ? q[s].x : 0.0;
     ov[s] = ok[s] ? q[s].y : 0.0;
-    oc[s] = s_cam + (ok[s] ? cam : C) * ACS_CAM_STRIDE;
+    oc[s] = s_cam + (ok[s] ? cam : C) * CS;
     mine += ok[s] ? 1 : 0;
   }
   // a point without any observation: no lane of its group has one (the lanes of a dead
@@ -215,7 +220,9 @@ __global__ __launch_bounds__(256) void k_sba_lm(const double2* __restrict__ uv,
     for (int s = 0; s < S; ++s) {
       // slots without an observation: the null camera, exact zero contributions
       double pu, pv, J[6];
-      if constexpr (HOIST)
+      if constexpr (MODEL == ACS_MODEL_STANDARD)
+        standard_uvj(oc[s], X0, X1, X2, pu, pv, J);
+      else if constexpr (HOIST)
         fisheye_uvj(cr[s], X0, X1, X2, pu, pv, J);
       else
         fisheye_uvj(oc[s], X0, X1, X2, pu, pv, J);
@@ -520,6 +527,7 @@ __global__ void k_scatter_slots(const int32_t* __restrict__ skey, const int32_t*
 
 
 // residual vector in the caller's observation order (cost_func_points_only, src/lib/sba.py:149-153)
+template <int MODEL>
 __global__ __launch_bounds__(256) void k_residuals_ext(const double* __restrict__ cams, int n_cams,
                                                        const double* __restrict__ uvobs,
                                                        const int32_t* __restrict__ pt_idx,
@@ -535,7 +543,7 @@ __global__ __launch_bounds__(256) void k_residuals_ext(const double* __restrict_
     return;
   }
   ProjOut o;
-  fisheye_project<false>(cams + c * ACS_CAM_STRIDE, pts[3 * p], pts[3 * p + 1], pts[3 * p + 2], o);
+  model_project<MODEL, false>(cams + c * CamRec<MODEL>::stride, pts[3 * p], pts[3 * p + 1], pts[3 * p + 2], o);
   res[2 * i] = o.u - uvobs[2 * i];
   res[2 * i + 1] = o.v - uvobs[2 * i + 1];
 }
@@ -546,14 +554,15 @@ static int next_pow2(int v) {
   return g;
 }
 
-template <int G, int S, bool CAMID>
+template <int G, int S, bool CAMID, int MODEL>
 static void launch_lm_t(acs_ctx* ctx, int blocks, int block, const double* cams, int C, int K, const double2* uv,
                         const uint8_t* mask, const uint8_t* camid, int64_t n_pts, const double* pts_in, double* pts,
                         SbaParams prm, double* c0, double* c1, int* st) {
   // register-resident camera records when the grid holds at most 2 waves per SIMD
   const int64_t waves = (n_pts * G + 63) / 64;
-  const bool hoist = S == 1 && !CAMID && G <= 16 && waves <= 8 * (int64_t)ctx->n_cu;
-  if constexpr (S == 1 && !CAMID && G <= 16) {
+  // (fisheye records only: the standard model always takes the LDS-staged instance)
+  const bool hoist = MODEL == ACS_MODEL_FISHEYE && S == 1 && !CAMID && G <= 16 && waves <= 8 * (int64_t)ctx->n_cu;
+  if constexpr (MODEL == ACS_MODEL_FISHEYE && S == 1 && !CAMID && G <= 16) {
     if (hoist) {
       // one wave per block, the size the kernel assumes (what run_lm picks for every grid of
       // fewer than 2 waves per SIMD anyway)
@@ -565,18 +574,19 @@ static void launch_lm_t(acs_ctx* ctx, int blocks, int block, const double* cams,
       return;
     }
   }
-  hipLaunchKernelGGL((k_sba_lm<G, S, CAMID, false>), dim3(blocks), dim3(block), sizeof(double) * ACS_CAM_STRIDE * (C + 1),
-                     ctx->stream, uv, mask, n_pts, pts_in, cams, K, C, camid, pts, prm, c0, c1, st);
+  hipLaunchKernelGGL((k_sba_lm<G, S, CAMID, false, 0, MODEL>), dim3(blocks), dim3(block),
+                     sizeof(double) * CamRec<MODEL>::stride * (C + 1), ctx->stream, uv, mask, n_pts, pts_in, cams, K, C,
+                     camid, pts, prm, c0, c1, st);
 }
 
-template <int S, bool CAMID>
+template <int S, bool CAMID, int MODEL>
 static int launch_lm_g(acs_ctx* ctx, int G, int blocks, int block, const double* cams, int C, int K,
                        const double2* uv, const uint8_t* mask, const uint8_t* camid, int64_t n_pts,
                        const double* pts_in, double* pts, SbaParams prm, double* c0, double* c1, int* st) {
   switch (G) {
 #define ACS_G(g)                                                                                      \
   case g:                                                                                             \
-    launch_lm_t<g, S, CAMID>(ctx, blocks, block, cams, C, K, uv, mask, camid, n_pts, pts_in, pts, prm, c0, c1, st); \
+    launch_lm_t<g, S, CAMID, MODEL>(ctx, blocks, block, cams, C, K, uv, mask, camid, n_pts, pts_in, pts, prm, c0, c1, st); \
     break;
     ACS_G(2) ACS_G(4) ACS_G(8) ACS_G(16) ACS_G(32) ACS_G(64)
 #undef ACS_G
@@ -591,8 +601,9 @@ static int launch_lm_g(acs_ctx* ctx, int G, int blocks, int block, const double*
 // latency-bound grids: at one point per 16-lane row, at most one wave per SIMD. There the
 // kernel lasts as long as its slowest wave, and the lanes a row leaves empty cost nothing.
 // ctx->sba_lm_layout (acs_sba_set_lm_layout) forces either instance where both are legal.
-static bool lm_row_selected(const acs_ctx* ctx, int K, int64_t n_pts, bool camid) {
-  const bool legal = !camid && K >= 3 && K <= 8;
+// Never legal for the standard model, which has no ROW (or HOIST) instance.
+static bool lm_row_selected(const acs_ctx* ctx, int K, int64_t n_pts, bool camid, int model = ACS_MODEL_FISHEYE) {
+  const bool legal = model == ACS_MODEL_FISHEYE && !camid && K >= 3 && K <= 8;
   if (!legal || ctx->sba_lm_layout == ACS_SBA_LM_BUTTERFLY) return false;
   if (ctx->sba_lm_layout == ACS_SBA_LM_ROW) return true;
   return (n_pts * 16 + 63) / 64 <= 4 * (int64_t)ctx->n_cu;
@@ -614,9 +625,25 @@ static void launch_lm_row(acs_ctx* ctx, const double* cams, int C, int K, const 
 #undef ACS_ROW_LAUNCH
 }
 
+// The S and camera-id instances of one model.
+template <int MODEL>
+static int launch_lm_s(acs_ctx* ctx, int S, int G, int blocks, int block, const double* dcams, int C, int K,
+                       const double2* duv, const uint8_t* dmask, const uint8_t* dcamid, int64_t n_pts,
+                       const double* dpts_in, double* dpts, SbaParams prm, double* c0, double* c1, int* st) {
+#define ACS_LM_ARGS ctx, G, blocks, block, dcams, C, K, duv, dmask, dcamid, n_pts, dpts_in, dpts, prm, c0, c1, st
+  if (dcamid)
+    return (S == 1) ? launch_lm_g<1, true, MODEL>(ACS_LM_ARGS)
+           : (S == 3) ? launch_lm_g<3, true, MODEL>(ACS_LM_ARGS)
+                      : launch_lm_g<4, true, MODEL>(ACS_LM_ARGS);
+  return (S == 1) ? launch_lm_g<1, false, MODEL>(ACS_LM_ARGS)
+         : (S == 3) ? launch_lm_g<3, false, MODEL>(ACS_LM_ARGS)
+                    : launch_lm_g<4, false, MODEL>(ACS_LM_ARGS);
+#undef ACS_LM_ARGS
+}
+
 // Launch the LM kernel over an (n_pts, K) slot tensor already on the device; initial points
-// from dpts_in, solution to dpts (may alias).
-static int run_lm(acs_ctx* ctx, const double* dcams, int C, int K, const double2* duv, const uint8_t* dmask,
+// from dpts_in, solution to dpts (may alias). model: ACS_MODEL_* of the camera records.
+static int run_lm(acs_ctx* ctx, int model, const double* dcams, int C, int K, const double2* duv, const uint8_t* dmask,
                   const uint8_t* dcamid, int64_t n_pts, const double* dpts_in, double* dpts,
                   const acs_sba_opts* opts, bool report, double** c0_out,
                   double** c1_out, int** st_out) {
@@ -635,7 +662,7 @@ static int run_lm(acs_ctx* ctx, const double* dcams, int C, int K, const double2
     st = (int*)acs_ws(ctx, WS_PERPT_I, sizeof(int) * 3 * n_pts);
     if (!c0 || !c1 || !st) return ACS_E_NOMEM;
   }
-  if (lm_row_selected(ctx, K, n_pts, dcamid != nullptr)) {
+  if (lm_row_selected(ctx, K, n_pts, dcamid != nullptr, model)) {
     launch_lm_row(ctx, dcams, C, K, duv, dmask, n_pts, dpts_in, dpts, prm, c0, c1, st);
     ACS_HIP(ctx, hipGetLastError());
     *c0_out = c0;
@@ -663,22 +690,11 @@ static int run_lm(acs_ctx* ctx, const double* dcams, int C, int K, const double2
   int block = 256;
   if (threads < (int64_t)256 * 2 * ctx->n_cu) block = 64;  // small problem: spread over more CUs
   const int blocks = acs_grid(threads, block);
-  int rc;
-  if (dcamid) {
-    rc = (S == 1) ? launch_lm_g<1, true>(ctx, G, blocks, block, dcams, C, K, duv, dmask, dcamid, n_pts, dpts_in, dpts, prm,
-                                         c0, c1, st)
-         : (S == 3) ? launch_lm_g<3, true>(ctx, G, blocks, block, dcams, C, K, duv, dmask, dcamid, n_pts, dpts_in, dpts,
-                                           prm, c0, c1, st)
-                    : launch_lm_g<4, true>(ctx, G, blocks, block, dcams, C, K, duv, dmask, dcamid, n_pts, dpts_in, dpts,
-                                           prm, c0, c1, st);
-  } else {
-    rc = (S == 1) ? launch_lm_g<1, false>(ctx, G, blocks, block, dcams, C, K, duv, dmask, dcamid, n_pts, dpts_in, dpts,
-                                          prm, c0, c1, st)
-         : (S == 3) ? launch_lm_g<3, false>(ctx, G, blocks, block, dcams, C, K, duv, dmask, dcamid, n_pts, dpts_in,
-                                            dpts, prm, c0, c1, st)
-                    : launch_lm_g<4, false>(ctx, G, blocks, block, dcams, C, K, duv, dmask, dcamid, n_pts, dpts_in,
-                                            dpts, prm, c0, c1, st);
-  }
+  const int rc = model == ACS_MODEL_STANDARD
+                     ? launch_lm_s<ACS_MODEL_STANDARD>(ctx, S, G, blocks, block, dcams, C, K, duv, dmask, dcamid, n_pts,
+                                                       dpts_in, dpts, prm, c0, c1, st)
+                     : launch_lm_s<ACS_MODEL_FISHEYE>(ctx, S, G, blocks, block, dcams, C, K, duv, dmask, dcamid, n_pts,
+                                                      dpts_in, dpts, prm, c0, c1, st);
   if (rc) return rc;
   ACS_HIP(ctx, hipGetLastError());
   *c0_out = c0;
@@ -700,7 +716,7 @@ static int run_report(acs_ctx* ctx, const double* c0, const double* c1, const in
 
 int acs_sba_dense_enqueue(acs_ctx* ctx, const double* dcams, int C, const double2* duv, const uint8_t* dmask,
                           int64_t n_pts, const double* dpts_in, double* dpts_out, const acs_sba_opts* opts,
-                          acs_report* report) {
+                          acs_report* report, int model) {
   if (n_pts == 0) {
     if (report) std::memset(report, 0, sizeof(*report));
     return ACS_OK;
@@ -708,7 +724,7 @@ int acs_sba_dense_enqueue(acs_ctx* ctx, const double* dcams, int C, const double
   double *c0, *c1;
   int* st;
   int rc;
-  if ((rc = run_lm(ctx, dcams, C, C, duv, dmask, nullptr, n_pts, dpts_in, dpts_out, opts, report != nullptr, &c0, &c1,
+  if ((rc = run_lm(ctx, model, dcams, C, C, duv, dmask, nullptr, n_pts, dpts_in, dpts_out, opts, report != nullptr, &c0, &c1,
                    &st)))
     return rc;
   if (report) return run_report(ctx, c0, c1, st, n_pts, report);
@@ -779,6 +795,14 @@ int acs_sba_lm_layout(const acs_ctx* ctx, int32_t n_slots, int64_t n_pts, int32_
   return lm_row_selected(ctx, n_slots, n_pts, with_cam_ids != 0) ? ACS_SBA_LM_ROW : ACS_SBA_LM_BUTTERFLY;
 }
 
+int acs_sba_lm_layout_flags(const acs_ctx* ctx, int32_t n_slots, int64_t n_pts, int32_t with_cam_ids, int32_t* n_cu,
+                            uint32_t flags) {
+  if (!ctx || n_slots < 1 || n_pts < 0) return -1;
+  if (n_cu) *n_cu = ctx->n_cu;
+  return lm_row_selected(ctx, n_slots, n_pts, with_cam_ids != 0, acs_flags_model(flags)) ? ACS_SBA_LM_ROW
+                                                                                         : ACS_SBA_LM_BUTTERFLY;
+}
+
 int acs_sba_points_dense_io(acs_ctx* ctx, const double* cams, int32_t n_cams, const double* uv,
                             const uint8_t* mask, int64_t n_pts, const double* pts_in, double* pts_out,
                             const acs_sba_opts* opts, acs_report* report, uint32_t flags) {
@@ -791,7 +815,8 @@ int acs_sba_points_dense_io(acs_ctx* ctx, const double* cams, int32_t n_cams, co
   }
   void *dc, *duv, *dm, *dpi;
   int rc;
-  if ((rc = acs_stage_in(ctx, WS_CAMS, cams, sizeof(double) * ACS_CAM_STRIDE * n_cams, flags, &dc))) return rc;
+  const int model = acs_flags_model(flags);
+  if ((rc = acs_stage_in(ctx, WS_CAMS, cams, sizeof(double) * acs_cam_stride(model) * n_cams, flags, &dc))) return rc;
   if ((rc = acs_stage_in(ctx, WS_UV, uv, sizeof(double) * 2 * n_pts * n_cams, flags, &duv))) return rc;
   if ((rc = acs_stage_in(ctx, WS_MASK, mask, (size_t)n_pts * n_cams, flags, &dm))) return rc;
   if ((rc = acs_stage_in(ctx, WS_PTS, pts_in, sizeof(double) * 3 * n_pts, flags, &dpi))) return rc;
@@ -799,7 +824,7 @@ int acs_sba_points_dense_io(acs_ctx* ctx, const double* cams, int32_t n_cams, co
   if (!dpo) return ACS_E_NOMEM;
   double *c0, *c1;
   int* st;
-  if ((rc = run_lm(ctx, (const double*)dc, n_cams, n_cams, (const double2*)duv, (const uint8_t*)dm, nullptr, n_pts,
+  if ((rc = run_lm(ctx, model, (const double*)dc, n_cams, n_cams, (const double2*)duv, (const uint8_t*)dm, nullptr, n_pts,
                    (const double*)dpi, dpo, opts, report != nullptr, &c0, &c1, &st)))
     return rc;
   if ((rc = acs_stage_out(ctx, pts_out, dpo, sizeof(double) * 3 * n_pts, flags))) return rc;
@@ -829,7 +854,9 @@ int acs_sba_points(acs_ctx* ctx, const double* cams, int32_t n_cams, const doubl
   }
   void *dc, *duv, *dpi, *dci, *dp;
   int rc;
-  if ((rc = acs_stage_in(ctx, WS_CAMS, cams, sizeof(double) * ACS_CAM_STRIDE * n_cams, flags, &dc))) return rc;
+  const int model = acs_flags_model(flags);
+  const auto k_res = model == ACS_MODEL_STANDARD ? k_residuals_ext<ACS_MODEL_STANDARD> : k_residuals_ext<ACS_MODEL_FISHEYE>;
+  if ((rc = acs_stage_in(ctx, WS_CAMS, cams, sizeof(double) * acs_cam_stride(model) * n_cams, flags, &dc))) return rc;
   if ((rc = acs_stage_in(ctx, WS_UV, uv, sizeof(double) * 2 * n_obs, flags, &duv))) return rc;
   if ((rc = acs_stage_in(ctx, WS_PTIDX, pt_idx, sizeof(int32_t) * n_obs, flags, &dpi))) return rc;
   if ((rc = acs_stage_in(ctx, WS_CAMIDX, cam_idx, sizeof(int32_t) * n_obs, flags, &dci))) return rc;
@@ -841,7 +868,7 @@ int acs_sba_points(acs_ctx* ctx, const double* cams, int32_t n_cams, const doubl
   if (resid_before) {
     drb = (double*)acs_out_buf(ctx, WS_OUT0, resid_before, sizeof(double) * 2 * n_obs, flags);
     if (!drb) return ACS_E_NOMEM;
-    hipLaunchKernelGGL(k_residuals_ext, dim3(acs_grid(n_obs, 256)), dim3(256), 0, s, (const double*)dc, n_cams,
+    hipLaunchKernelGGL(k_res, dim3(acs_grid(n_obs, 256)), dim3(256), 0, s, (const double*)dc, n_cams,
                        (const double*)duv, (const int32_t*)dpi, (const int32_t*)dci, n_obs, (const double*)dp, n_pts,
                        drb);
     ACS_HIP(ctx, hipGetLastError());
@@ -856,7 +883,7 @@ int acs_sba_points(acs_ctx* ctx, const double* cams, int32_t n_cams, const doubl
 
   double *c0, *c1;
   int* st;
-  if ((rc = run_lm(ctx, (const double*)dc, n_cams, K, uvp, mk, cid, n_pts, (const double*)dp, (double*)dp, opts,
+  if ((rc = run_lm(ctx, model, (const double*)dc, n_cams, K, uvp, mk, cid, n_pts, (const double*)dp, (double*)dp, opts,
                    report != nullptr, &c0, &c1, &st)))
     return rc;
 
@@ -864,7 +891,7 @@ int acs_sba_points(acs_ctx* ctx, const double* cams, int32_t n_cams, const doubl
   if (resid_after) {
     dra = (double*)acs_out_buf(ctx, WS_OUT1, resid_after, sizeof(double) * 2 * n_obs, flags);
     if (!dra) return ACS_E_NOMEM;
-    hipLaunchKernelGGL(k_residuals_ext, dim3(acs_grid(n_obs, 256)), dim3(256), 0, s, (const double*)dc, n_cams,
+    hipLaunchKernelGGL(k_res, dim3(acs_grid(n_obs, 256)), dim3(256), 0, s, (const double*)dc, n_cams,
                        (const double*)duv, (const int32_t*)dpi, (const int32_t*)dci, n_obs, (const double*)dp, n_pts,
                        dra);
     ACS_HIP(ctx, hipGetLastError());

@@ -513,6 +513,7 @@ int acs_sba_extrinsics(acs_ctx* ctx, double* cams, int32_t n_cams, const double*
                        const acs_sba_ext_opts* opts, double* resid_before, double* resid_after,
                        acs_sba_ext_report* report, uint32_t flags) {
   ACS_DEVICE_GUARD(ctx);
+  ACS_FISHEYE_ONLY(ctx, flags, "acs_sba_extrinsics");
   acs_sba_ext_opts op;
   acs_sba_ext_default_opts(&op);
   if (opts) op = *opts;
@@ -845,6 +846,7 @@ int acs_sba_ext_dist_create(acs_ctx* ctx, const double* cams, int32_t n_cams, co
                             int64_t n_pts, const acs_sba_ext_opts* opts, int32_t rank, int32_t world,
                             acs_sba_ext_dist** out, int64_t* payload_sizes, uint32_t flags) {
   ACS_DEVICE_GUARD(ctx);
+  ACS_FISHEYE_ONLY(ctx, flags, "acs_sba_ext_dist_create");
   acs_sba_ext_opts op;
   acs_sba_ext_default_opts(&op);
   if (opts) op = *opts;

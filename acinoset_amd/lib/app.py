@@ -1,4 +1,4 @@
-"""Mirror of the SBA / FTE seams of src/lib/app.py: `sba_points_fisheye` (:135-138),
+"""Mirror of the SBA / FTE seams of src/lib/app.py: `sba_points_standard` (:129-132), `sba_points_fisheye` (:135-138),
 `sba_board_points_fisheye` (:123-126), `save_tri` (:238-268), `save_sba` (:271-295),
 `save_ekf` (:298-314), `save_fte` (:317-332), `start_logging` / `stop_logging` (:337-345).
 The save functions write the pickle/.mat outputs and, when `cam[1-9].mp4` sit beside the
@@ -12,8 +12,12 @@ from glob import glob
 import numpy as np
 
 from . import misc, utils
-from .calib import project_points_fisheye, triangulate_points_fisheye
+from .calib import project_points, project_points_fisheye, triangulate_points, triangulate_points_fisheye
 from .sba import _sba_board_points, _sba_points
+
+
+def sba_points_standard(scene_fpath, points_2d_df):
+    return _sba_points(scene_fpath, points_2d_df, triangulate_points, project_points)
 
 
 def sba_points_fisheye(scene_fpath, points_2d_df):
@@ -53,26 +57,29 @@ def _with_directions(positions, markers):
     return np.concatenate((positions, head[:, None], gaze[:, None]), axis=1)
 
 
-def save_tri(positions, out_dir, scene_fpath, markers, start_frame, errors, save_videos=True) -> str:
+def save_tri(positions, out_dir, scene_fpath, markers, start_frame, errors, save_videos=True,
+             project_func=None) -> str:
     """`src/lib/app.py:238-268`: tri.pickle = {positions (N, L+2, 3), start_frame, errors}
-    (+ tri.mat without the error tables) and the cam*_tri reprojections."""
+    (+ tri.mat without the error tables) and the cam*_tri reprojections (through
+    `project_func`; None = the fisheye projection)."""
     n_vid = len(_videos(out_dir))
     positions = _with_directions(positions, markers)
     out_fpath = os.path.join(out_dir, 'tri.pickle')
     utils.save_optimised_cheetah(positions, out_fpath, extra_data=dict(start_frame=start_frame, errors=errors))
-    utils.save_3d_cheetah_as_2d([positions] * n_vid, out_dir, scene_fpath, markers, project_points_fisheye,
-                                start_frame)
+    utils.save_3d_cheetah_as_2d([positions] * n_vid, out_dir, scene_fpath, markers,
+                                project_func or project_points_fisheye, start_frame)
     return out_fpath
 
 
-def save_sba(positions, out_dir, scene_fpath, markers, start_frame, save_videos=True) -> str:
-    """`src/lib/app.py:271-295`: sba.pickle (+ .mat) and the cam*_sba reprojections."""
+def save_sba(positions, out_dir, scene_fpath, markers, start_frame, save_videos=True, project_func=None) -> str:
+    """`src/lib/app.py:271-295`: sba.pickle (+ .mat) and the cam*_sba reprojections (through
+    `project_func`; None = the fisheye projection)."""
     n_vid = len(_videos(out_dir))
     positions = _with_directions(positions, markers)
     out_fpath = os.path.join(out_dir, 'sba.pickle')
     utils.save_optimised_cheetah(positions, out_fpath, extra_data=dict(start_frame=start_frame))
-    utils.save_3d_cheetah_as_2d([positions] * n_vid, out_dir, scene_fpath, markers, project_points_fisheye,
-                                start_frame)
+    utils.save_3d_cheetah_as_2d([positions] * n_vid, out_dir, scene_fpath, markers,
+                                project_func or project_points_fisheye, start_frame)
     return out_fpath
 
 

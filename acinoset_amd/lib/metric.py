@@ -13,7 +13,10 @@ from . import calib
 COLUMNS = ['frame', 'marker', 'camera_distance', 'pixel_residual', 'pck_threshold', 'error_u', 'error_v']
 
 
-def residual_error(points_2d_df, points_3d_dfs, markers, camera_params) -> Dict:
+def residual_error(points_2d_df, points_3d_dfs, markers, camera_params, project_func=None) -> Dict:
+    """`project_func` (reference signature; None = `calib.project_points_fisheye`) projects the
+    3-D points: pass `calib.project_points` for a standard-model scene."""
+    project = project_func or calib.project_points_fisheye
     k_arr, d_arr, r_arr, t_arr, _, _ = camera_params
     n_cam = len(k_arr)
     if not isinstance(points_3d_dfs, list):
@@ -45,7 +48,7 @@ def residual_error(points_2d_df, points_3d_dfs, markers, camera_params) -> Dict:
             pck = n2e_df.reindex(v)['distance'].to_numpy()
             pts2 = p2[['x', 'y']].to_numpy(np.float64)
             pts3 = p3[['x', 'y', 'z']].to_numpy(np.float64)
-            prj = calib.project_points_fisheye(pts3, k_arr[i], d_arr[i], r_arr[i], t_arr[i])
+            prj = project(pts3, k_arr[i], d_arr[i], r_arr[i], t_arr[i])
             cam_dist = np.sqrt(np.sum((pts3 - np.squeeze(t_arr[i])) ** 2, axis=1))
             err = pts2 - prj
             dfs.append(pd.DataFrame({'frame': p2['frame'].to_numpy(), 'marker': m, 'camera_distance': cam_dist,

@@ -17,6 +17,7 @@ from time import time
 import numpy as np
 
 from .. import _native
+from . import calib
 from .utils import get_pairwise_3d_points_from_df, load_manual_points, load_points, load_scene, save_scene
 
 
@@ -40,27 +41,41 @@ def create_bundle_adjustment_jacobian_sparsity_matrix(n_cams, n_params_per_camer
     return A
 
 
-def _cams(k_arr, d_arr, r_arr, t_arr):
+def is_standard_model(func):
+    """Whether a `project_func` / `triangulate_func` argument selects the standard (pinhole)
+    model: only `calib.project_points` and `calib.triangulate_points` themselves do. None and
+    the fisheye functions select the fisheye model, and so does any other callable (it is not
+    called: the model is built into the kernels)."""
+    return func is calib.project_points or func is calib.triangulate_points
+
+
+def _cams(k_arr, d_arr, r_arr, t_arr, standard=False):
     n = len(k_arr)
+    if standard:
+        return _native.pack_cameras_standard(k_arr, d_arr, r_arr, np.asarray(t_arr).reshape(n, 3))
     return _native.pack_cameras(k_arr, np.asarray(d_arr).reshape(n, 4), r_arr, np.asarray(t_arr).reshape(n, 3))
 
 
 def cost_func_points_only(params, n_points, point_3d_indices, camera_indices, k_arr, d_arr, r_arr, t_arr, points_2d,
                           project_func=None):
+    """`src/lib/sba.py:149-153`. `project_func is calib.project_points` selects the standard
+    model; None, the fisheye function and any other callable the fisheye model."""
     obj = np.asarray(params, np.float64).reshape(n_points, 3)
-    return _native.default_context().sba_residuals(_cams(k_arr, d_arr, r_arr, t_arr), points_2d, point_3d_indices,
-                                                   camera_indices, obj)
+    cams = _cams(k_arr, d_arr, r_arr, t_arr, is_standard_model(project_func))
+    return _native.default_context().sba_residuals(cams, points_2d, point_3d_indices, camera_indices, obj)
 
 
 def bundle_adjust_points_only(points_2d, points_3d, point_3d_indices, camera_indices, k_arr, d_arr, r_arr, t_arr,
                               project_func=None, f_scale=50, **opts):
-    """Points-only robust BA. `project_func` is accepted for signature compatibility: the
-    fisheye model is built into the kernel (src/lib/app.py:135-138 passes
-    project_points_fisheye)."""
+    """Points-only robust BA. Both camera models are built into the kernel and `project_func`
+    selects between them: `calib.project_points` (src/lib/app.py:129-132) runs the standard
+    model; None and `calib.project_points_fisheye` (src/lib/app.py:135-138) the fisheye model,
+    and so does any other callable, which is never called."""
     ctx = _native.default_context()
     o = ctx.sba_opts(f_scale=float(f_scale), **opts)
     t0 = time()
-    pts, rb, ra, rep = ctx.sba_points(_cams(k_arr, d_arr, r_arr, t_arr), np.asarray(points_2d, np.float64),
+    cams = _cams(k_arr, d_arr, r_arr, t_arr, is_standard_model(project_func))
+    pts, rb, ra, rep = ctx.sba_points(cams, np.asarray(points_2d, np.float64),
                                       np.asarray(point_3d_indices), np.asarray(camera_indices),
                                       np.asarray(points_3d, np.float64), o)
     t1 = time()
@@ -71,10 +86,11 @@ def bundle_adjust_points_only(points_2d, points_3d, point_3d_indices, camera_ind
 
 
 def _sba_points(scene_fpath, points_2d_df, triangulate_func=None, project_func=None):
-    """`src/lib/sba.py:285-313`."""
+    """`src/lib/sba.py:285-313`. `calib.triangulate_points` / `calib.project_points` select the
+    standard model for the initialisation / the solve (see bundle_adjust_points_only)."""
     k_arr, d_arr, r_arr, t_arr, cam_res = load_scene(scene_fpath)
-    points_3d_df = get_pairwise_3d_points_from_df(points_2d_df, k_arr, d_arr.reshape((-1, 4)), r_arr, t_arr,
-                                                  triangulate_func)
+    d_tri = d_arr if is_standard_model(triangulate_func) else d_arr.reshape((-1, 4))
+    points_3d_df = get_pairwise_3d_points_from_df(points_2d_df, k_arr, d_tri, r_arr, t_arr, triangulate_func)
     points_3d_df['point_index'] = points_3d_df.index
     points_3d = np.array(points_3d_df[['x', 'y', 'z']], dtype=np.float64)
     points_df = points_2d_df.merge(points_3d_df, how='inner', on=['frame', 'marker'], suffixes=('_cam', ''))
@@ -143,7 +159,7 @@ def cost_func_points_extrinsics(params, n_cams, n_points, point_3d_indices, came
     """`src/lib/sba.py:142-146`."""
     obj, r_arr, t_arr = params_to_points_extrinsics(np.asarray(params, np.float64), n_cams, n_points)
     return cost_func_points_only(obj.ravel(), n_points, point_3d_indices, camera_indices, k_arr, d_arr, r_arr, t_arr,
-                                 points_2d)
+                                 points_2d, project_func)
 
 
 def bundle_adjust_points_and_extrinsics(points_2d, points_3d, point_3d_indices, camera_indices, k_arr, d_arr, r_arr,
@@ -152,7 +168,11 @@ def bundle_adjust_points_and_extrinsics(points_2d, points_3d, point_3d_indices, 
     translation refined together (intrinsics fixed) on the same Cauchy objective (scipy's
     default f_scale = 1). Returns (obj_pts (n,3), r_arr (C,3,3), t_arr (C,3,1),
     {'before', 'after'}) like the reference; rotations stay orthonormal matrices (updated
-    on SO(3), which is what the reference's Rodrigues round trip represents)."""
+    on SO(3), which is what the reference's Rodrigues round trip represents).
+    Fisheye model only: `project_func=calib.project_points` raises NotImplementedError."""
+    if is_standard_model(project_func):
+        raise NotImplementedError('bundle_adjust_points_and_extrinsics: the standard camera model is built for the '
+                                  'points-only SBA only (the joint solve would silently use the fisheye model)')
     ctx = _native.default_context()
     n = len(k_arr)
     o = ctx.sba_ext_opts(f_scale=float(f_scale), **opts)
@@ -173,16 +193,18 @@ def bundle_adjust_points_and_extrinsics(points_2d, points_3d, point_3d_indices, 
 
 def _triangulate_batch(jobs, k_arr, d_arr, r_arr, t_arr, triangulate_func):
     """jobs: [(uv_a (n,2), uv_b (n,2), cam_a, cam_b)] -> list of (n, 3). The fisheye model
-    (triangulate_func None or calib.triangulate_points_fisheye) runs as ONE GPU batch;
-    any other triangulate_func is called per job, as the reference does."""
+    (triangulate_func None or calib.triangulate_points_fisheye) and the standard model
+    (calib.triangulate_points) run as ONE GPU batch; any other triangulate_func is called per
+    job, as the reference does."""
     from .calib import triangulate_points_fisheye
     if not jobs:
         return []
-    if triangulate_func is not None and triangulate_func is not triangulate_points_fisheye:
+    standard = is_standard_model(triangulate_func)
+    if triangulate_func is not None and triangulate_func is not triangulate_points_fisheye and not standard:
         return [np.asarray(triangulate_func(a, b, k_arr[ca], d_arr[ca], r_arr[ca], t_arr[ca],
                                             k_arr[cb], d_arr[cb], r_arr[cb], t_arr[cb])).reshape(-1, 3)
                 for a, b, ca, cb in jobs]
-    cams = _native.pack_cameras(k_arr, np.asarray(d_arr).reshape(-1, 4), r_arr, t_arr)
+    cams = _cams(k_arr, d_arr, r_arr, t_arr, standard)
     uva = np.concatenate([np.asarray(a, np.float64).reshape(-1, 2) for a, _, _, _ in jobs])
     uvb = np.concatenate([np.asarray(b, np.float64).reshape(-1, 2) for _, b, _, _ in jobs])
     cia = np.concatenate([np.full(len(np.asarray(a).reshape(-1, 2)), ca, np.int32) for a, _, ca, _ in jobs])

@@ -290,10 +290,15 @@ def get_pairwise_3d_points_from_df(points_2d_df, k_arr, d_arr, r_arr, t_arr, tri
     """`src/lib/utils.py:319-349` with the GPU triangulation: for adjacent camera pairs
     (i, i+1 mod C), inner join on (frame, marker), triangulate, then mean per
     (frame, marker) in pair order. Returns [frame, marker, x, y, z] sorted by
-    (frame, marker) like the reference's groupby. `triangulate_func` is accepted for
-    signature compatibility (the fisheye model is always used)."""
+    (frame, marker) like the reference's groupby. `triangulate_func is calib.triangulate_points`
+    selects the standard model (d_arr then holds 4, 5 or 8 coefficients per camera); None,
+    `calib.triangulate_points_fisheye` and any other callable (never called) the fisheye model."""
+    from . import calib
     n_cams = len(k_arr)
-    cams = _native.pack_cameras(k_arr, np.asarray(d_arr).reshape(-1, 4), r_arr, t_arr)
+    if triangulate_func is calib.triangulate_points:
+        cams = _native.pack_cameras_standard(k_arr, d_arr, r_arr, t_arr)
+    else:
+        cams = _native.pack_cameras(k_arr, np.asarray(d_arr).reshape(-1, 4), r_arr, t_arr)
     parts = []
     for ca in range(n_cams):
         cb = (ca + 1) % n_cams

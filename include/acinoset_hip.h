@@ -33,6 +33,7 @@ extern "C" {
 
 #define ACS_ABI_VERSION 5
 #define ACS_CAM_STRIDE 20
+#define ACS_CAM_STRIDE_STD 24 /* standard (pinhole) camera records, see ACS_CAMS_STANDARD */
 
 /* status codes */
 #define ACS_OK 0
@@ -43,6 +44,13 @@ extern "C" {
 
 /* flags */
 #define ACS_DEVICE_PTRS 1u  /* array arguments are device pointers; call is async */
+/* `cams` holds standard-model (cv::projectPoints) records of ACS_CAM_STRIDE_STD doubles:
+ *   [fx, fy, cx, cy, k1, k2, p1, p2, k3, k4, k5, k6, R00..R22 (row-major), t0, t1, t2]
+ * (a shorter OpenCV coefficient vector zero-padded; skew ignored). Accepted by acs_project_standard,
+ * acs_sba_residuals, acs_sba_points, acs_sba_points_dense[_io], acs_triangulate_pairs and
+ * acs_triangulate_dense; every other entry point that takes cameras returns ACS_E_INVALID
+ * when the bit is set.                                                                   */
+#define ACS_CAMS_STANDARD 2u
 
 /* per-problem convergence status (acs_report.status_counts index / oracle/sba.py) */
 /* acs_ekf_run / acs_sba_ekf_pipeline measurement-model mode (their ref_numerics argument) */
@@ -104,6 +112,15 @@ int acs_project_fisheye(acs_ctx* ctx, const double* cams, int32_t n_cams, const 
                         const int32_t* cam_idx, int64_t n, int32_t fte_form, double* uv_out,
                         uint32_t flags);
 
+/* ---- standard-model projection (project_points, src/lib/calib.py:65-67) --------------
+ * As acs_project_fisheye for ACS_CAM_STRIDE_STD records (ACS_CAMS_STANDARD is implied and
+ * may be set): a = Y0/Y2, b = Y1/Y2, r2 = a^2 + b^2,
+ *   cd = (1 + k1 r2 + k2 r2^2 + k3 r2^3) / (1 + k4 r2 + k5 r2^2 + k6 r2^3)
+ *   u = fx (a cd + 2 p1 a b + p2 (r2 + 2 a^2)) + cx,  v = fy (b cd + p1 (r2 + 2 b^2) + 2 p2 a b) + cy
+ * with no guard on Y2 (a point behind the camera projects by the same formula, as OpenCV's). */
+int acs_project_standard(acs_ctx* ctx, const double* cams, int32_t n_cams, const double* pts,
+                         const int32_t* cam_idx, int64_t n, double* uv_out, uint32_t flags);
+
 /* ---- a2: SBA residual vector (cost_func_points_only, src/lib/sba.py:149-153) -------
  * resid[2i+d] = project(cams[cam_idx[i]], pts[pt_idx[i]])[d] - uv[2i+d]              */
 int acs_sba_residuals(acs_ctx* ctx, const double* cams, int32_t n_cams, const double* uv,
@@ -146,6 +163,10 @@ int acs_sba_set_lm_layout(acs_ctx* ctx, int32_t layout);
  * n_cu (may be NULL) receives the CU count the selection works with.                        */
 int acs_sba_lm_layout(const acs_ctx* ctx, int32_t n_slots, int64_t n_pts, int32_t with_cam_ids,
                       int32_t* n_cu);
+/* The same for a solve whose call carries `flags`: with ACS_CAMS_STANDARD always
+ * ACS_SBA_LM_BUTTERFLY (the standard model has the LDS-staged butterfly instances only). */
+int acs_sba_lm_layout_flags(const acs_ctx* ctx, int32_t n_slots, int64_t n_pts, int32_t with_cam_ids,
+                            int32_t* n_cu, uint32_t flags);
 
 /* ---- a9: redescending loss (src/lib/misc.py:329-343), elementwise ------------------ */
 int acs_redescending_loss(acs_ctx* ctx, const double* err, int64_t n, double a, double b, double c,
@@ -298,7 +319,10 @@ int acs_fte_dist_destroy(acs_fte_dist* h);
  * are kept), so a timed multi-GPU solve reuses one handle per rank. */
 int acs_fte_dist_reset(acs_fte_dist* h, const double* X, const double* tau, uint32_t flags);
 
-/* ---- next: fisheye triangulation -------------------------------------
+/* ---- next: triangulation ---------------------------------------------
+ * With ACS_CAMS_STANDARD the views are undistorted as triangulate_points does
+ * (src/lib/calib.py:53-62): cv::undistortPoints with its default criteria, exactly 5
+ * fixed-point iterations and no convergence test; the DLT is the same.
  * acs_triangulate_pairs: triangulate_points_fisheye (src/lib/calib.py:120-129) for n
  * (view a, view b) pairs; uv_a/uv_b (n, 2) pixels, cam_a/cam_b (n) camera ids, out (n, 3).
  * acs_triangulate_dense: get_pairwise_3d_points_from_df (src/lib/utils.py:319-349) on the

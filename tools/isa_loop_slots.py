@@ -23,7 +23,7 @@ import sys
 from collections import Counter
 
 CLASSES = ('f64', 'dpp', 'vector', 'scalar', 'memory', 'other')
-DEFAULT = '_Z8k_sba_lmILi16ELi1ELb0ELb1ELi3EE'
+DEFAULT = '_Z8k_sba_lmILi16ELi1ELb0ELb1ELi3ELi0EE'
 
 
 def classify(mn):
