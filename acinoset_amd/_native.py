@@ -30,6 +30,7 @@ ACS_CAM_STRIDE = 20
 ACS_CAM_STRIDE_STD = 24    # [fx fy cx cy k1 k2 p1 p2 k3 k4 k5 k6 R(9) t(3)]
 CAMERA_MODELS = {'fisheye': ACS_CAM_STRIDE, 'standard': ACS_CAM_STRIDE_STD}
 STATUS_NAMES = ('running', 'gtol', 'ftol', 'xtol', 'stalled', 'maxiter', 'noobs')
+ACS_COV_OK, ACS_COV_NOOBS, ACS_COV_DEGENERATE = 0, 1, 2   # per-point status of the SBA covariance
 SD_MODES = {'const': 0, 'variable': 1}        # src/core/fte.py:35 shutter_delay_mode
 
 SBA_LM_LAYOUTS = {'auto': 0, 'butterfly': 1, 'row': 2}   # ACS_SBA_LM_* of the header
@@ -49,6 +50,7 @@ SYMBOLS = (
     'acs_sba_ext_dist_result', 'acs_sba_ext_dist_destroy', 'acs_ekf_run',
     'acs_sba_ekf_pipeline', 'acs_fte_covariance', 'acs_sba_set_lm_layout', 'acs_sba_lm_layout',
     'acs_project_standard', 'acs_sba_lm_layout_flags',
+    'acs_sba_points_covariance', 'acs_sba_points_dense_covariance',
 )
 
 
@@ -123,6 +125,14 @@ class FteCovReport(C.Structure):
                 ('var_max', C.c_double)]
 
 
+class SbaCovReport(C.Structure):
+    _fields_ = [('n_points', C.c_int64), ('n_ok', C.c_int64), ('n_noobs', C.c_int64), ('n_degenerate', C.c_int64),
+                ('var_min', C.c_double), ('var_max', C.c_double), ('sigma_hat_px', C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class SbaExtOpts(C.Structure):
     _fields_ = [('max_iters', C.c_int32), ('reserved', C.c_int32), ('f_scale', C.c_double), ('ftol', C.c_double),
                 ('xtol', C.c_double), ('gtol', C.c_double), ('lambda0', C.c_double)]
@@ -167,6 +177,10 @@ def _declare(lib):
                                            u32]),
         'acs_sba_points_dense_io': (C.c_int, [_P, _P, i32, _P, _P, i64, _P, _P, C.POINTER(SbaOpts),
                                               C.POINTER(Report), u32]),
+        'acs_sba_points_covariance': (C.c_int, [_P, _P, i32, _P, _P, _P, i64, _P, i64, dbl, dbl, _P, _P,
+                                                C.POINTER(SbaCovReport), u32]),
+        'acs_sba_points_dense_covariance': (C.c_int, [_P, _P, i32, _P, _P, i64, _P, dbl, dbl, _P, _P,
+                                                      C.POINTER(SbaCovReport), u32]),
         'acs_sba_set_lm_layout': (C.c_int, [_P, i32]),
         'acs_sba_lm_layout': (C.c_int, [_P, i32, i64, i32, C.POINTER(i32)]),
         'acs_sba_lm_layout_flags': (C.c_int, [_P, i32, i64, i32, C.POINTER(i32), u32]),
@@ -487,6 +501,58 @@ class Context:
                                                   C.c_void_p(pts_p), C.byref(opts), rp, flags)
         self.check(rc, 'acs_sba_points_dense')
         return rep.as_dict() if rep is not None else None
+
+    # ---- per-point position covariance of the points-only SBA ---------------------------
+    def sba_points_covariance(self, cams, uv, pt_idx, cam_idx, pts, f_scale=50.0, sigma_px=1.0):
+        """acs_sba_points_covariance at `pts` (nothing is solved): cov (n, 3, 3) = sigma_px^2 times
+        the inverse of each point's undamped Triggs-weighted GN matrix, status (n,) int32
+        (ACS_COV_OK 0 / NOOBS 1 / DEGENERATE 2; cov is NaN unless OK) and the report dict
+        (n_points, n_ok, n_noobs, n_degenerate, var_min, var_max, sigma_hat_px). Observation
+        list as sba_points; the record width selects the camera model."""
+        cams, mf = _cams_flags(cams)
+        uv = _c64(uv).reshape(-1, 2)
+        pi = np.ascontiguousarray(pt_idx, np.int32)
+        ci = np.ascontiguousarray(cam_idx, np.int32)
+        pts = _c64(pts).reshape(-1, 3)
+        n = len(pts)
+        cov = np.empty((n, 3, 3))
+        status = np.empty(n, np.int32)
+        rep = SbaCovReport()
+        self.check(self.lib.acs_sba_points_covariance(self.h, _ptr(cams), len(cams), _ptr(uv), _ptr(pi), _ptr(ci),
+                                                      len(uv), _ptr(pts), n, float(f_scale), float(sigma_px),
+                                                      _ptr(cov), _ptr(status), C.byref(rep), mf),
+                   'acs_sba_points_covariance')
+        return cov, status, rep.as_dict()
+
+    def sba_points_dense_covariance(self, cams, uv, mask, pts, f_scale=50.0, sigma_px=1.0):
+        """The dense form (uv (n, C, 2), mask (n, C)) of sba_points_covariance."""
+        cams, mf = _cams_flags(cams)
+        C_ = len(cams)
+        uv = _c64(uv).reshape(-1, C_, 2)
+        mask = np.ascontiguousarray(mask, np.uint8).reshape(-1, C_)
+        pts = _c64(pts).reshape(-1, 3)
+        n = len(pts)
+        cov = np.empty((n, 3, 3))
+        status = np.empty(n, np.int32)
+        rep = SbaCovReport()
+        self.check(self.lib.acs_sba_points_dense_covariance(self.h, _ptr(cams), C_, _ptr(uv), _ptr(mask), n, _ptr(pts),
+                                                            float(f_scale), float(sigma_px), _ptr(cov), _ptr(status),
+                                                            C.byref(rep), mf), 'acs_sba_points_dense_covariance')
+        return cov, status, rep.as_dict()
+
+    def sba_points_dense_covariance_dev(self, cams_p, n_cams, uv_p, mask_p, n_pts, pts_p, cov_p, status_p=None,
+                                        f_scale=50.0, sigma_px=1.0, report=False, camera_model='fisheye'):
+        """Device-pointer variant (every array resident in HBM, cov (n, 3, 3) and the optional int32
+        status written there; only enqueues on the context stream unless `report`, which waits and
+        returns the report dict)."""
+        flags = ACS_DEVICE_PTRS | _model_flags(camera_model)
+        rep = SbaCovReport() if report else None
+        v = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+        self.check(self.lib.acs_sba_points_dense_covariance(self.h, v(cams_p), n_cams, v(uv_p), v(mask_p), n_pts,
+                                                            v(pts_p), float(f_scale), float(sigma_px), v(cov_p),
+                                                            v(status_p), C.byref(rep) if report else None, flags),
+                   'acs_sba_points_dense_covariance')
+        return rep.as_dict() if report else None
 
     # ---- a6 -------------------------------------------------------------------------
     def sba_ext_opts(self, **kw):

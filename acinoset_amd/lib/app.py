@@ -16,12 +16,13 @@ from .calib import project_points, project_points_fisheye, triangulate_points, t
 from .sba import _sba_board_points, _sba_points
 
 
-def sba_points_standard(scene_fpath, points_2d_df):
-    return _sba_points(scene_fpath, points_2d_df, triangulate_points, project_points)
+def sba_points_standard(scene_fpath, points_2d_df, covariance=False, sigma_px=1.0):
+    return _sba_points(scene_fpath, points_2d_df, triangulate_points, project_points, covariance, sigma_px)
 
 
-def sba_points_fisheye(scene_fpath, points_2d_df):
-    return _sba_points(scene_fpath, points_2d_df, triangulate_points_fisheye, project_points_fisheye)
+def sba_points_fisheye(scene_fpath, points_2d_df, covariance=False, sigma_px=1.0):
+    return _sba_points(scene_fpath, points_2d_df, triangulate_points_fisheye, project_points_fisheye, covariance,
+                       sigma_px)
 
 
 def sba_board_points_fisheye(scene_fpath, points_fpaths, out_fpath, manual_points_fpath=None, manual_points_only=False,
@@ -71,13 +72,15 @@ def save_tri(positions, out_dir, scene_fpath, markers, start_frame, errors, save
     return out_fpath
 
 
-def save_sba(positions, out_dir, scene_fpath, markers, start_frame, save_videos=True, project_func=None) -> str:
+def save_sba(positions, out_dir, scene_fpath, markers, start_frame, save_videos=True, project_func=None,
+             extra=None) -> str:
     """`src/lib/app.py:271-295`: sba.pickle (+ .mat) and the cam*_sba reprojections (through
-    `project_func`; None = the fisheye projection)."""
+    `project_func`; None = the fisheye projection). `extra` (a dict, optional) is merged into the
+    pickle's extra data (core.sba's covariance keys)."""
     n_vid = len(_videos(out_dir))
     positions = _with_directions(positions, markers)
     out_fpath = os.path.join(out_dir, 'sba.pickle')
-    utils.save_optimised_cheetah(positions, out_fpath, extra_data=dict(start_frame=start_frame))
+    utils.save_optimised_cheetah(positions, out_fpath, extra_data=dict(start_frame=start_frame, **(extra or {})))
     utils.save_3d_cheetah_as_2d([positions] * n_vid, out_dir, scene_fpath, markers,
                                 project_func or project_points_fisheye, start_frame)
     return out_fpath

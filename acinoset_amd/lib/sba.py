@@ -66,11 +66,14 @@ def cost_func_points_only(params, n_points, point_3d_indices, camera_indices, k_
 
 
 def bundle_adjust_points_only(points_2d, points_3d, point_3d_indices, camera_indices, k_arr, d_arr, r_arr, t_arr,
-                              project_func=None, f_scale=50, **opts):
+                              project_func=None, f_scale=50, covariance=False, sigma_px=1.0, **opts):
     """Points-only robust BA. Both camera models are built into the kernel and `project_func`
     selects between them: `calib.project_points` (src/lib/app.py:129-132) runs the standard
     model; None and `calib.project_points_fisheye` (src/lib/app.py:135-138) the fisheye model,
-    and so does any other callable, which is never called."""
+    and so does any other callable, which is never called.
+    `covariance=True` adds to the returned dict `cov` (n, 3, 3) in m^2, `cov_status` (n,) and
+    `cov_report` (acs_sba_points_covariance at the solved points, same f_scale, pixel noise
+    `sigma_px`); the points and residuals are those of the plain call."""
     ctx = _native.default_context()
     o = ctx.sba_opts(f_scale=float(f_scale), **opts)
     t0 = time()
@@ -82,12 +85,21 @@ def bundle_adjust_points_only(points_2d, points_3d, point_3d_indices, camera_ind
     print(f'GPU SBA: {rep["n_problems"]} points, iters max {rep["iters_max"]}, cost {rep["cost_before"]:.4e} -> '
           f'{rep["cost_after"]:.4e}, status {rep["status_counts"]}')
     print(f'\nOptimization took {t1 - t0:.2f} seconds')
-    return pts, dict(before=rb, after=ra)
+    res = dict(before=rb, after=ra)
+    if covariance:
+        cov, cst, crep = ctx.sba_points_covariance(cams, np.asarray(points_2d, np.float64),
+                                                   np.asarray(point_3d_indices), np.asarray(camera_indices), pts,
+                                                   f_scale=float(f_scale), sigma_px=float(sigma_px))
+        print(f'GPU SBA covariance: {crep["n_ok"]} ok, {crep["n_degenerate"]} degenerate, {crep["n_noobs"]} without '
+              f'observations; sigma_hat {crep["sigma_hat_px"]:.4f} px (sigma_px {float(sigma_px):g})')
+        res.update(cov=cov, cov_status=cst, cov_report=crep)
+    return pts, res
 
 
-def _sba_points(scene_fpath, points_2d_df, triangulate_func=None, project_func=None):
+def _sba_points(scene_fpath, points_2d_df, triangulate_func=None, project_func=None, covariance=False, sigma_px=1.0):
     """`src/lib/sba.py:285-313`. `calib.triangulate_points` / `calib.project_points` select the
-    standard model for the initialisation / the solve (see bundle_adjust_points_only)."""
+    standard model for the initialisation / the solve (see bundle_adjust_points_only).
+    With `covariance`, res['cov'] / res['cov_status'] rows follow the returned DataFrame's rows."""
     k_arr, d_arr, r_arr, t_arr, cam_res = load_scene(scene_fpath)
     d_tri = d_arr if is_standard_model(triangulate_func) else d_arr.reshape((-1, 4))
     points_3d_df = get_pairwise_3d_points_from_df(points_2d_df, k_arr, d_tri, r_arr, t_arr, triangulate_func)
@@ -99,7 +111,8 @@ def _sba_points(scene_fpath, points_2d_df, triangulate_func=None, project_func=N
     camera_indices = np.array(points_df['camera'])
     print('bundle_adjust_points_only')
     pts_3d, res = bundle_adjust_points_only(points_2d, points_3d, point_indices, camera_indices, k_arr, d_arr, r_arr,
-                                            t_arr, project_func, f_scale=50)
+                                            t_arr, project_func, f_scale=50, covariance=covariance,
+                                            sigma_px=sigma_px)
     print(f"\nBefore: mean: {np.mean(res['before'])}, std: {np.std(res['before'])}")
     print(f"After: mean: {np.mean(res['after'])}, std: {np.std(res['after'])}\n")
     new_points_3d_df = points_3d_df.copy()

@@ -47,9 +47,9 @@ extern "C" {
 /* `cams` holds standard-model (cv::projectPoints) records of ACS_CAM_STRIDE_STD doubles:
  *   [fx, fy, cx, cy, k1, k2, p1, p2, k3, k4, k5, k6, R00..R22 (row-major), t0, t1, t2]
  * (a shorter OpenCV coefficient vector zero-padded; skew ignored). Accepted by acs_project_standard,
- * acs_sba_residuals, acs_sba_points, acs_sba_points_dense[_io], acs_triangulate_pairs and
- * acs_triangulate_dense; every other entry point that takes cameras returns ACS_E_INVALID
- * when the bit is set.                                                                   */
+ * acs_sba_residuals, acs_sba_points, acs_sba_points_dense[_io], acs_sba_points_covariance,
+ * acs_sba_points_dense_covariance, acs_triangulate_pairs and acs_triangulate_dense; every other
+ * entry point that takes cameras returns ACS_E_INVALID when the bit is set.               */
 #define ACS_CAMS_STANDARD 2u
 
 /* per-problem convergence status (acs_report.status_counts index / oracle/sba.py) */
@@ -148,6 +148,41 @@ int acs_sba_points_dense(acs_ctx* ctx, const double* cams, int32_t n_cams, const
 int acs_sba_points_dense_io(acs_ctx* ctx, const double* cams, int32_t n_cams, const double* uv,
                             const uint8_t* mask, int64_t n_pts, const double* pts_in, double* pts_out,
                             const acs_sba_opts* opts, acs_report* report, uint32_t flags);
+
+/* ---- per-point position covariance of the points-only SBA -----------------------------
+ * For point i with observations o, residuals r_od (pixels) at `pts`, z = r^2 / f_scale^2 and
+ * w = 1 / (1 + z):
+ *   H_i = sum_o sum_d wh_od J_od^T J_od,  wh = max((1 - z) w^2, 0.1 w)
+ * (the solver's own Triggs-weighted Gauss-Newton matrix, undamped, evaluated at the points
+ * passed in: nothing is solved here), and
+ *   cov_i = sigma_px^2 H_i^-1   (m^2; sigma_px = the pixel noise the caller assumes, e.g. 1).
+ * The inverse is an LDL^T without pivoting with pivots d0, d1, d2; the point is DEGENERATE when
+ * any pivot fails d > 1e-9 max(H00, H11, H22) (a NaN fails it): a point seen by one camera, or
+ * by cameras on one line with it. status (int32 per point, may be NULL) is ACS_COV_*; for a
+ * status other than ACS_COV_OK all nine entries of the point's cov are NaN. cov (n_pts, 3, 3)
+ * is exactly symmetric. The report (may be NULL; waits for the stream) counts the statuses
+ * and gives the extreme marginal variances over the OK points and the a-posteriori pixel scale
+ *   sigma_hat_px^2 = sum w r^2 / (m - 3 n_ok)
+ * over the observations of the OK points, m their number of scalar residuals (NaN when
+ * m <= 3 n_ok): reported, never applied to cov. Observation layouts, ACS_CAMS_STANDARD and
+ * ACS_DEVICE_PTRS as acs_sba_points / acs_sba_points_dense; with device pointers and no report
+ * the call only enqueues on the context stream.                                          */
+#define ACS_COV_OK 0
+#define ACS_COV_NOOBS 1
+#define ACS_COV_DEGENERATE 2
+typedef struct {
+  int64_t n_points, n_ok, n_noobs, n_degenerate;
+  double var_min, var_max;  /* extreme diagonal entries of cov over the OK points (NaN: none) */
+  double sigma_hat_px;
+} acs_sba_cov_report;
+int acs_sba_points_covariance(acs_ctx* ctx, const double* cams, int32_t n_cams, const double* uv,
+                              const int32_t* pt_idx, const int32_t* cam_idx, int64_t n_obs,
+                              const double* pts, int64_t n_pts, double f_scale, double sigma_px,
+                              double* cov, int32_t* status, acs_sba_cov_report* report, uint32_t flags);
+int acs_sba_points_dense_covariance(acs_ctx* ctx, const double* cams, int32_t n_cams, const double* uv,
+                                    const uint8_t* mask, int64_t n_pts, const double* pts, double f_scale,
+                                    double sigma_px, double* cov, int32_t* status,
+                                    acs_sba_cov_report* report, uint32_t flags);
 
 /* Test hook: which instance of the LM kernel a points-only solve of this context launches.
  * AUTO (the default) takes the row instance (one point per 16-lane row, row-broadcast sums) for
