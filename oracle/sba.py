@@ -24,7 +24,10 @@ Marquardt damping H + lam*diag(H); accept only on strict cost decrease. Spec sha
           accepted and (dF <= ftol*F or |dx| <= xtol*(xtol+|x|))
           | rejected and |dx| <= xtol*(xtol+|x|) | lam > 1e16 | iters >= max_iters
     A damped matrix that is not positive definite yields no step: the iteration counts as
-    a rejection (lam *= 10, no trial evaluation, no xtol test).
+    a rejection (lam *= 10, no trial evaluation, no xtol test). A matrix that is not finite
+    (a NaN start point or observation) is not positive definite: such a point ends STALLED
+    after 20 passes with its one initial evaluation, and no other point is touched.
+    A point without observations is NOOBS: untouched, no pass and no evaluation.
 """
 import numpy as np
 
@@ -96,8 +99,14 @@ def sba_points(points_2d, points_3d, point_idx, cam_idx, K, D, R, t, f_scale=50.
     has = valid.sum(1) > 0
     status = np.where(has, RUNNING, NOOBS)
     iters = np.zeros(n_pts, np.int64)
-    nfev = np.ones(n_pts, np.int64)
+    nfev = has.astype(np.int64)                         # a point without observations is never evaluated
     lam = np.full(n_pts, 1e-3)
+    # value / bound of the stopping tests of each point's last pass (gtol, cost resolution, ftol,
+    # xtol); NaN where the pass did not come to the test. <= 1 is a test that fired (or would have,
+    # had one of higher priority not): how far from its bound a point's status was decided. The ftol
+    # column is (F - Fn) / (ftol F) of every trial, negative or zero for a rejected one: how far
+    # from rounding the accept decision itself was
+    margins = np.full((n_pts, 4), np.nan)
     F, H, g = linearize(x)
     cost_before = F.copy()
     for _ in range(max_iters):
@@ -105,6 +114,8 @@ def sba_points(points_2d, points_3d, point_idx, cam_idx, K, D, R, t, f_scale=50.
         if not act.any():
             break
         gmax = np.abs(g).max(1)
+        margins[act] = np.nan
+        margins[act, 0] = gmax[act] / gtol
         done = act & (gmax <= gtol)
         status[done] = GTOL
         act &= ~done
@@ -124,6 +135,9 @@ def sba_points(points_2d, points_3d, point_idx, cam_idx, K, D, R, t, f_scale=50.
                     ok[j] = True
                 except np.linalg.LinAlgError:
                     pass
+        # a non-finite matrix (a NaN start point or observation) is not positive definite either:
+        # LAPACK may hand back a NaN factor for it without an error
+        ok &= np.isfinite(L).all((1, 2))
         ia = np.nonzero(act)[0]
         dx = np.zeros((n_pts, 3))
         y = np.linalg.solve(np.where(ok[:, None, None], L, np.eye(3)), -g[ia][..., None])
@@ -133,6 +147,8 @@ def sba_points(points_2d, points_3d, point_idx, cam_idx, K, D, R, t, f_scale=50.
         pred = -np.einsum('ni,ni->n', g, dx) - 0.5 * np.einsum('ni,nij,nj->n', dx, H, dx)
         res = np.zeros(n_pts, bool)
         res[ia] = ok & (pred[ia] <= COST_RES * F[ia])
+        with np.errstate(invalid='ignore', divide='ignore'):
+            margins[ia, 1] = np.where(ok, pred[ia] / (COST_RES * F[ia]), np.nan)
         status[res] = FTOL
         act &= ~res
         dx[res] = 0.0
@@ -150,6 +166,10 @@ def sba_points(points_2d, points_3d, point_idx, cam_idx, K, D, R, t, f_scale=50.
         # the xtol test needs a step: only where the Cholesky succeeded
         small = pdm & (np.linalg.norm(dx, axis=1) <= xtol * (xtol + np.linalg.norm(x, axis=1)))
         ftol_hit = accept & ((F - Fn) <= ftol * F)
+        with np.errstate(invalid='ignore', divide='ignore'):
+            margins[:, 2] = np.where(trial, (F - Fn) / (ftol * F), margins[:, 2])
+            margins[:, 3] = np.where(act & pdm, np.linalg.norm(dx, axis=1) / (xtol * (xtol + np.linalg.norm(x, axis=1))),
+                                     margins[:, 3])
         x = np.where(accept[:, None], xn, x)
         lam = np.where(accept, np.maximum(lam * 0.1, 1e-15), np.where(reject, lam * 10.0, lam))
         if accept.any():
@@ -163,7 +183,8 @@ def sba_points(points_2d, points_3d, point_idx, cam_idx, K, D, R, t, f_scale=50.
         status[reject & ~small & (lam > 1e16)] = STALLED
     status[status == RUNNING] = MAXITER
     if return_info:
-        return x, dict(status=status, iters=iters, nfev=nfev, cost_before=cost_before, cost_after=F)
+        return x, dict(status=status, iters=iters, nfev=nfev, cost_before=cost_before, cost_after=F,
+                       margins=margins)
     return x
 
 

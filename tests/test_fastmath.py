@@ -1,7 +1,11 @@
 """CPU: the short-latency f64 helpers of acinoset_amd/csrc/fastmath.hpp (log1p_pos, the
 rcp/rsq wrappers), built with g++ from the same header the kernels include and checked
 against libm. On the device rcp_nr / rsq_nr refine the hardware estimates by two Newton
-steps; the GPU parity tests cover that path end to end."""
+steps (NaN at 0, where the host forms below give +-inf) and atan_pos runs on the same hardware
+reciprocal: tests/test_gpu_camera_edges.py covers those device forms at their edges (the optical
+axis and OpenCV's guard around rsq_nr, the camera's plane for rcp_nr(0), atan_pos's range limits
+tan(pi/8) and tan(3 pi/8) with their float64 neighbours, arguments up to 1e6); the other GPU
+parity tests cover them on mid-field inputs."""
 import os
 import shutil
 import subprocess

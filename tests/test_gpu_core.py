@@ -161,6 +161,27 @@ def test_sba_single_observation_points(ctx):
     assert got['gtol'] + got['xtol'] == ref['gtol'] + ref['xtol'] and abs(got['gtol'] - ref['gtol']) <= 1, (got, ref)
     assert np.abs(ra).max() < 1e-9  # reprojects exactly (the depth along the ray is free)
     assert np.abs(pts - x_or).max() < 1e-6
+    # Point by point: each of the 64 solved alone (a point's place in the wave does not change its
+    # result: test_gpu_sba_lanes.py) must end with the oracle's status. Only the boundary point may
+    # differ, between gtol and xtol and at the oracle's position; the aggregate is then the oracle's
+    # with that one point's label exchanged, exactly.
+    BOUNDARY = 20
+    alone = np.empty(n, np.int64)
+    for p in range(n):
+        one, _, _, rp = ctx.sba_points(_cams(g), uv[p:p + 1], np.zeros(1, np.int32), ci[p:p + 1], X[p:p + 1],
+                                       residuals=False)
+        hit = [k for k in names if rp['status_counts'][k]]
+        assert len(hit) == 1 and rp['n_problems'] == 1, rp
+        alone[p] = names.index(hit[0])
+        np.testing.assert_array_equal(one[0].view(np.uint64), pts[p].view(np.uint64))
+    others = np.arange(n) != BOUNDARY
+    np.testing.assert_array_equal(alone[others], info['status'][others])
+    assert info['status'][BOUNDARY] in (osba.GTOL, osba.XTOL) and alone[BOUNDARY] in (osba.GTOL, osba.XTOL)
+    assert np.abs(pts[BOUNDARY] - x_or[BOUNDARY]).max() < 1e-12
+    want = np.bincount(np.where(others, info['status'], alone[BOUNDARY]), minlength=7)
+    assert got == dict(zip(names, want.tolist())), (got, ref)
+    print('single-observation points: boundary point %d is %s on the GPU, %s in the oracle' % (
+        BOUNDARY, names[alone[BOUNDARY]], names[info['status'][BOUNDARY]]))
 
 
 def test_sba_dense_io_matches_inplace(ctx):
