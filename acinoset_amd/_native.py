@@ -51,6 +51,7 @@ SYMBOLS = (
     'acs_sba_ekf_pipeline', 'acs_fte_covariance', 'acs_sba_set_lm_layout', 'acs_sba_lm_layout',
     'acs_project_standard', 'acs_sba_lm_layout_flags',
     'acs_sba_points_covariance', 'acs_sba_points_dense_covariance',
+    'acs_sba_ext_cov_default_opts', 'acs_sba_extrinsics_covariance',
 )
 
 
@@ -149,6 +150,25 @@ class SbaExtReport(C.Structure):
         return d
 
 
+GAUGES = {'free': 0, 'anchor': 1}   # ACS_GAUGE_* of the header
+
+
+class SbaExtCovOpts(C.Structure):
+    _fields_ = [('gauge', C.c_int32), ('anchor_cam', C.c_int32), ('scale_cam', C.c_int32), ('reserved', C.c_int32),
+                ('f_scale', C.c_double), ('sigma_px', C.c_double)]
+
+
+class SbaExtCovReport(C.Structure):
+    _fields_ = [('status', C.c_int32), ('reserved', C.c_int32), ('n_points', C.c_int64), ('n_ok', C.c_int64),
+                ('n_noobs', C.c_int64), ('n_degenerate', C.c_int64), ('dof', C.c_int64), ('min_pivot', C.c_double),
+                ('sigma_hat_px', C.c_double), ('rot_sd_max', C.c_double), ('trans_sd_max', C.c_double)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != 'reserved'}
+        d['status_name'] = 'degenerate' if self.status else 'ok'
+        return d
+
+
 # must equal ACS_ABI_VERSION in include/acinoset_hip.h (checked when the library loads)
 ABI_VERSION = 5
 _lib = None
@@ -181,6 +201,9 @@ def _declare(lib):
                                                 C.POINTER(SbaCovReport), u32]),
         'acs_sba_points_dense_covariance': (C.c_int, [_P, _P, i32, _P, _P, i64, _P, dbl, dbl, _P, _P,
                                                       C.POINTER(SbaCovReport), u32]),
+        'acs_sba_ext_cov_default_opts': (None, [C.POINTER(SbaExtCovOpts)]),
+        'acs_sba_extrinsics_covariance': (C.c_int, [_P, _P, i32, _P, _P, _P, i64, _P, i64, C.POINTER(SbaExtCovOpts),
+                                                    _P, _P, _P, C.POINTER(SbaExtCovReport), u32]),
         'acs_sba_set_lm_layout': (C.c_int, [_P, i32]),
         'acs_sba_lm_layout': (C.c_int, [_P, i32, i64, i32, C.POINTER(i32)]),
         'acs_sba_lm_layout_flags': (C.c_int, [_P, i32, i64, i32, C.POINTER(i32), u32]),
@@ -577,6 +600,35 @@ class Context:
                                                _ptr(pts), len(pts), C.byref(opts), _ptr(rb), _ptr(ra),
                                                C.byref(rep), _std_flag(cams)), 'acs_sba_extrinsics')
         return cams, pts, rb, ra, rep.as_dict()
+
+    def sba_extrinsics_covariance(self, cams, uv, pt_idx, cam_idx, pts, f_scale=1.0, sigma_px=1.0, gauge='anchor',
+                                  anchor=(0, 1), points=True):
+        """acs_sba_extrinsics_covariance at (`cams`, `pts`) (nothing is solved): the covariance of the
+        camera poses in the chosen gauge and the joint covariance of every point. Returns
+        (cov_cams (6C, 6C), cov_points (n, 3, 3) or None, status (n,) int32, report dict).
+        cov_cams rows 6c..6c+5 are camera c's (dw, dt): R <- exp([dw]x) R (rad), t <- t + dt (m).
+        gauge 'free': inner constraints over the camera parameters (sigma^2 pinv(S)); 'anchor':
+        camera anchor[0]'s pose and the distance between the centres of anchor[0] and anchor[1]
+        held (camera anchor[0]'s rows and columns are exact zeros). A degenerate problem
+        (report['status'] = 1) returns NaN everywhere. `f_scale` is the solve's."""
+        if gauge not in GAUGES:
+            raise ValueError(f"gauge must be 'free' or 'anchor', not {gauge!r}")
+        cams = _c64(cams)
+        uv = _c64(uv).reshape(-1, 2)
+        pi = np.ascontiguousarray(pt_idx, np.int32)
+        ci = np.ascontiguousarray(cam_idx, np.int32)
+        pts = _c64(pts).reshape(-1, 3)
+        n, nc = len(pts), len(cams)
+        o = SbaExtCovOpts(GAUGES[gauge], int(anchor[0]), int(anchor[1]), 0, float(f_scale), float(sigma_px))
+        cov_c = np.empty((6 * nc, 6 * nc))
+        cov_p = np.empty((n, 3, 3)) if points else None
+        status = np.empty(n, np.int32)
+        rep = SbaExtCovReport()
+        self.check(self.lib.acs_sba_extrinsics_covariance(self.h, _ptr(cams), nc, _ptr(uv), _ptr(pi), _ptr(ci), len(uv),
+                                                          _ptr(pts), n, C.byref(o), _ptr(cov_c), _ptr(cov_p),
+                                                          _ptr(status), C.byref(rep), _std_flag(cams)),
+                   'acs_sba_extrinsics_covariance')
+        return cov_c, cov_p, status, rep.as_dict()
 
     # ---- f2: EKF + RTS smoother ----------------------------------------------------------
     def ekf_run(self, table, cams, meas, likelihood, fps, thresh, max_pixel_err, r_std_base, Q, P0, s0,

@@ -22,9 +22,8 @@
 #include <algorithm>
 
 #include "mfma64.hpp"
+#include "sba_ext.hpp"
 
-#define EXT_MAXC 16
-#define EXT_CHUNK 64
 #define EXT_Q 45  // per slot: U (21 packed upper) + g_c (6) + W (18)
 // damping floor: the 7-DoF similarity gauge is left free (as in the reference), so the
 // reduced camera system is singular up to lambda; below ~1e-8 its gauge directions are
@@ -50,15 +49,6 @@ struct ExtOpts {
   int max_iters;
   double ftol, xtol, gtol;
 };
-
-__device__ __forceinline__ int upk(int i, int j) {  // packed upper-triangular index, 6x6
-  if (i > j) {
-    const int t = i;
-    i = j;
-    j = t;
-  }
-  return i * 6 - i * (i - 1) / 2 + (j - i);
-}
 
 template <int G>
 __global__ __launch_bounds__(256) void k_ext_linearize(ExtDims d, const ExtState* __restrict__ st,
@@ -546,8 +536,7 @@ int acs_sba_extrinsics(acs_ctx* ctx, double* cams, int32_t n_cams, const double*
   int G = 2;
   while (G < K) G <<= 1;
   d.G = G;
-  // points per Schur block: W M tiles of a chunk must fit ~96 KB of LDS
-  d.chunk = std::max(1, std::min(EXT_CHUNK, (int)(96 * 1024 / (148 * K + 24))));
+  d.chunk = ext_chunk_points(K);
   const int nchunk = (int)((n_pts + d.chunk - 1) / d.chunk);
   const int NC = 6 * n_cams, nE = NC * NC + 3 * NC;
   size_t off = 0;
@@ -874,7 +863,7 @@ int acs_sba_ext_dist_create(acs_ctx* ctx, const double* cams, int32_t n_cams, co
   ExtDims& d = h->d;
   d = ExtDims{(int)n_pts, K, n_cams, 2, EXT_CHUNK, op.f_scale * op.f_scale};
   while (d.G < K) d.G <<= 1;
-  d.chunk = std::max(1, std::min(EXT_CHUNK, (int)(96 * 1024 / (148 * K + 24))));
+  d.chunk = ext_chunk_points(K);
   h->nchunk = (int)((n_pts + d.chunk - 1) / d.chunk);
   h->R = world;
   h->rank = rank;

@@ -1,0 +1,736 @@
+// sba_ext_cov.hip — camera-pose and joint point covariances of the points + extrinsics SBA
+// (sba_ext.hip) on gfx950.
+//
+// Definition (include/acinoset_hip.h), everything at the state passed in:
+//   per camera (dw, dt): R <- exp([dw]x) R, t <- t + dt; J_cam = J_Y [-[R X]x | I], J_pt = J_Y R;
+//   wh = max((1 - z) w^2, 0.1 w), w = 1 / (1 + z), z = r^2 / f_scale^2 (k_ext_linearize's).
+//   Point status on its own V = sum wh J_pt^T J_pt (k_sba_cov's rule); a point that is not OK is
+//   left out entirely. S = sum U - sum_OK W V^-1 W^T, undamped, symmetrised.
+//   Gauge generators G (6C x 7): rotation dw = -R_c theta; translation dt = -R_c tau; scale
+//   dt = t_c. Q = orth(G), mu = max diag S, Ah = S + mu Q Q^T scaled to unit diagonal.
+//   FREE:   cov = sigma^2 [(S + mu Q Q^T)^-1 - Q Q^T / mu]
+//   ANCHOR: cov = P cov_free P^T, P = I - Q (Cm Q)^-1 Cm, Cm = [I_6 on camera a; h on camera b],
+//           h = e^T [-R_b^T [t_b]x | -R_b^T], e the unit baseline of the centres c = -R^T t.
+//   Degenerate: G of rank < 7, or a pivot of the unpivoted LDL^T of Ah fails d > 1e-9.
+//   Point i: cov_i = sigma^2 V_i^-1 + V_i^-1 B_i^T cov_cc B_i V_i^-1.
+//
+// Kernels:
+//   k_extcov_linearize<G> [point groups] one point per aligned lane group (k_ext_linearize's
+//                   mapping): per slot U (21 packed) and W (18); per point V summed over the
+//                   group, its status, V^-1 (LDL^T, k_sba_cov's) and the sigma_hat terms
+//   k_extcov_schur  [point chunks] fixed-order chunk partials of S over the OK points
+//                   (k_ext_schur's scheme, no atomics)
+//   k_extcov_cams   [1 block] chunk sums in order, symmetrise, G and its Gram-Schmidt, mu,
+//                   Jacobi scaling, scalar LDL^T pivot test, SPD inverse on the f64 MFMA tiles
+//                   (wg_spd_inverse) with one refinement step, unscale, - Q Q^T / mu, anchor
+//                   transform, mirror, sigma^2, the report
+//   k_extcov_points<G> [point groups] cov_cc staged in LDS; lane l owns slot l: T = sum_o'
+//                   cov_cc[c_o, c_o'] W_o', then W_o^T T, group_sum, lane 0 writes the record
+#include "mfma64.hpp"
+#include "sba_ext.hpp"
+
+#define XC_Q 39  // per slot: U (21 packed upper) + W (18)
+#define XC_PIVOT_TOL 1e-9
+
+struct XcDims {
+  int n, K, C, chunk;
+  double f2;
+};
+
+template <int G>
+__global__ __launch_bounds__(256) void k_extcov_linearize(XcDims d, const double* __restrict__ cams,
+                                                          const double* __restrict__ pts,
+                                                          const double2* __restrict__ uv,
+                                                          const uint8_t* __restrict__ mask,
+                                                          const uint8_t* __restrict__ camid, double* __restrict__ Q,
+                                                          double* __restrict__ Vi, int32_t* __restrict__ status,
+                                                          double* __restrict__ wr2, int32_t* __restrict__ nres) {
+  __shared__ double s_cam[EXT_MAXC * ACS_CAM_STRIDE];
+  for (int i = threadIdx.x; i < d.C * ACS_CAM_STRIDE; i += blockDim.x) s_cam[i] = cams[i];
+  __syncthreads();
+  const int lane = threadIdx.x & (G - 1);
+  const int64_t p = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / G;
+  if (p >= d.n) return;  // whole group leaves together
+  const double X0 = pts[3 * p], X1 = pts[3 * p + 1], X2 = pts[3 * p + 2];
+  // V (packed upper: 00 01 02 11 12 22), sum w r^2, number of scalar residuals
+  double v[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) v[i] = 0.0;
+  for (int slot = lane; slot < d.K; slot += G) {
+    const int64_t o = p * d.K + slot;
+    double* q = Q + (size_t)o * XC_Q;
+    if (!mask[o] || camid[o] >= d.C) {
+      for (int e = 0; e < XC_Q; ++e) q[e] = 0.0;
+      continue;
+    }
+    const double* c = s_cam + camid[o] * ACS_CAM_STRIDE;
+    ProjOut po;
+    fisheye_project<true>(c, X0, X1, X2, po);
+    const double2 m = uv[o];
+    const double r[2] = {po.u - m.x, po.v - m.y};
+    // R X = Y - t
+    const double v0 = po.Y[0] - c[17], v1 = po.Y[1] - c[18], v2 = po.Y[2] - c[19];
+    double U[21], W[18];
+    for (int e = 0; e < 21; ++e) U[e] = 0.0;
+    for (int e = 0; e < 18; ++e) W[e] = 0.0;
+    for (int dd = 0; dd < 2; ++dd) {
+      const double* jy = po.JY + 3 * dd;
+      const double* jp = po.J + 3 * dd;
+      // J_cam = [-(J_Y [v]x), J_Y]
+      const double jc[6] = {-(jy[1] * v2 - jy[2] * v1), -(jy[2] * v0 - jy[0] * v2), -(jy[0] * v1 - jy[1] * v0),
+                            jy[0], jy[1], jy[2]};
+      const double rr = r[dd] * r[dd];
+      const double z = rr / d.f2;
+      const double w = 1.0 / (1.0 + z);
+      const double wh = fmax((1.0 - z) * w * w, 0.1 * w);
+      for (int i = 0; i < 6; ++i) {
+        for (int j = i; j < 6; ++j) U[upk(i, j)] += wh * jc[i] * jc[j];
+        for (int j = 0; j < 3; ++j) W[i * 3 + j] += wh * jc[i] * jp[j];
+      }
+      v[0] += wh * jp[0] * jp[0];
+      v[1] += wh * jp[0] * jp[1];
+      v[2] += wh * jp[0] * jp[2];
+      v[3] += wh * jp[1] * jp[1];
+      v[4] += wh * jp[1] * jp[2];
+      v[5] += wh * jp[2] * jp[2];
+      v[6] += w * rr;
+    }
+    v[7] += 2.0;
+    for (int e = 0; e < 21; ++e) q[e] = U[e];
+    for (int e = 0; e < 18; ++e) q[21 + e] = W[e];
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) v[i] = group_sum<G>(v[i]);
+  if (lane != 0) return;
+  // LDL^T without pivoting (k_sba_cov's): V^-1 = sum_k (1 / d_k) m_k^T m_k, m_k the rows of L^-1
+  const double d0 = v[0], i0 = 1.0 / d0;
+  const double l10 = v[1] * i0, l20 = v[2] * i0;
+  const double d1 = v[3] - l10 * v[1], i1 = 1.0 / d1;
+  const double t = v[4] - l20 * v[1];
+  const double l21 = t * i1;
+  const double d2 = v[5] - l20 * v[2] - l21 * t, i2 = 1.0 / d2;
+  const double thr = XC_PIVOT_TOL * fmax(v[0], fmax(v[3], v[5]));
+  const bool ok = d0 > thr && d1 > thr && d2 > thr;  // a NaN pivot or threshold fails
+  const int st = v[7] == 0.0 ? ACS_COV_NOOBS : ok ? ACS_COV_OK : ACS_COV_DEGENERATE;
+  const bool good = st == ACS_COV_OK;
+  const double m20 = l10 * l21 - l20;
+  const double c22 = i2, c12 = -l21 * i2, c02 = m20 * i2;
+  const double c11 = i1 + l21 * l21 * i2;
+  const double c01 = -l10 * i1 - l21 * c02;
+  const double c00 = i0 + l10 * l10 * i1 + m20 * c02;
+  double* vi = Vi + (size_t)p * 6;  // V^-1, packed upper; zeros for a point that is left out
+  vi[0] = good ? c00 : 0.0;
+  vi[1] = good ? c01 : 0.0;
+  vi[2] = good ? c02 : 0.0;
+  vi[3] = good ? c11 : 0.0;
+  vi[4] = good ? c12 : 0.0;
+  vi[5] = good ? c22 : 0.0;
+  status[p] = st;
+  wr2[p] = good ? v[6] : 0.0;
+  nres[p] = good ? (int32_t)v[7] : 0;
+}
+
+// chunk partial of S (6C x 6C) over the OK points of the chunk, every entry summed in point and
+// slot order by one thread
+__global__ __launch_bounds__(256) void k_extcov_schur(XcDims d, const double* __restrict__ Q,
+                                                      const double* __restrict__ Vi,
+                                                      const int32_t* __restrict__ status,
+                                                      const uint8_t* __restrict__ mask,
+                                                      const uint8_t* __restrict__ camid, double* __restrict__ part) {
+  const int ch = blockIdx.x;
+  const int p0 = ch * d.chunk, p1 = min(d.n, p0 + d.chunk), np = p1 - p0;
+  const int NC = 6 * d.C, nE = NC * NC;
+  extern __shared__ double lds[];
+  double* sZ = lds;                                   // np x K x 18  (W V^-1)
+  int* scam = (int*)(sZ + (size_t)d.chunk * d.K * 18);  // np x K camera id (-1 = none / left out)
+  for (int t = threadIdx.x; t < np; t += blockDim.x) {
+    const int p = p0 + t;
+    const double* vi = Vi + (size_t)p * 6;
+    const double M[9] = {vi[0], vi[1], vi[2], vi[1], vi[3], vi[4], vi[2], vi[4], vi[5]};
+    const bool pok = status[p] == ACS_COV_OK;
+    for (int s = 0; s < d.K; ++s) {
+      const int64_t o = (int64_t)p * d.K + s;
+      const bool ok = pok && mask[o] && camid[o] < d.C;
+      scam[t * d.K + s] = ok ? camid[o] : -1;
+      const double* W = Q + (size_t)o * XC_Q + 21;
+      for (int i = 0; i < 6; ++i)
+        for (int j = 0; j < 3; ++j)
+          sZ[((size_t)t * d.K + s) * 18 + i * 3 + j] =
+              ok ? W[i * 3] * M[j] + W[i * 3 + 1] * M[3 + j] + W[i * 3 + 2] * M[6 + j] : 0.0;
+    }
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < nE; e += blockDim.x) {
+    double acc = 0.0;
+    const int a = e / NC, b = e % NC, c1 = a / 6, k1 = a % 6, c2 = b / 6, k2 = b % 6;
+    for (int t = 0; t < np; ++t) {
+      const int64_t base = (int64_t)(p0 + t) * d.K;
+      for (int s1 = 0; s1 < d.K; ++s1) {
+        if (scam[t * d.K + s1] != c1) continue;
+        if (c1 == c2) acc += Q[(size_t)(base + s1) * XC_Q + upk(k1, k2)];
+        const double* z = sZ + ((size_t)t * d.K + s1) * 18 + k1 * 3;
+        for (int s2 = 0; s2 < d.K; ++s2) {
+          if (scam[t * d.K + s2] != c2) continue;
+          const double* w = Q + (size_t)(base + s2) * XC_Q + 21 + k2 * 3;
+          acc -= z[0] * w[0] + z[1] * w[1] + z[2] * w[2];
+        }
+      }
+    }
+    part[(size_t)ch * nE + e] = acc;
+  }
+}
+
+// sum over the 64 lanes of a wave, the same bits in every lane
+__device__ __forceinline__ double wave_sum64(double v) {
+  for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+
+struct XcCamArgs {
+  int nchunk, gauge, a, b;
+  double s2;
+};
+
+// LDS of k_extcov_cams in doubles: S (NP x (NP + 1)), Q, K, MC (NP x 8 each), CM (8 x NP),
+// scale (NP), tile-inverse scratch (512), reductions (256), small (128), the report's counts (1024)
+static size_t extcov_cams_lds(int NP) {
+  return sizeof(double) * ((size_t)NP * (NP + 1) + 4 * (size_t)NP * 8 + NP + 512 + 256 + 128 + 1024);
+}
+
+__global__ __launch_bounds__(256) void k_extcov_cams(XcDims d, XcCamArgs ar, const double* __restrict__ part,
+                                                     const double* __restrict__ cams,
+                                                     const int32_t* __restrict__ status,
+                                                     const double* __restrict__ wr2, const int32_t* __restrict__ nres,
+                                                     double* __restrict__ Ag, double* __restrict__ T1,
+                                                     double* __restrict__ T2, double* __restrict__ cov,
+                                                     acs_sba_ext_cov_report* __restrict__ rep, int* __restrict__ bad) {
+  const int NC = 6 * d.C, NP = ((NC + 15) / 16) * 16, LD = NP + 1, nE = NC * NC;
+  const int tid = threadIdx.x;
+  extern __shared__ double lds[];
+  double* sS = lds;               // NP x LD
+  double* sQ = sS + NP * LD;      // NP x 8: G, then its orthonormal basis
+  double* sK = sQ + NP * 8;       // NP x 8: Q (Cm Q)^-1
+  double* sMC = sK + NP * 8;      // NP x 8: M Cm^T
+  double* sCM = sMC + NP * 8;     // 8 x NP: Cm M
+  double* ssc = sCM + 8 * NP;     // NP: Jacobi scaling
+  double* tmp = ssc + NP;         // 512
+  double* s_red = tmp + 512;      // 256
+  double* s_sm = s_red + 256;     // 128: [0] gauge rank flag, [1] mu, [2] anchor flag, 8.. h, 16.. (Cm Q)^-1
+  // 1. chunk sums in order (raw S to T1), then the symmetrised S to LDS
+  for (int e = tid; e < nE; e += blockDim.x) {
+    double v = 0.0;
+    for (int ch = 0; ch < ar.nchunk; ++ch) v += part[(size_t)ch * nE + e];
+    T1[e] = v;
+  }
+  __syncthreads();
+  for (int e = tid; e < NP * NP; e += blockDim.x) {
+    const int r = e / NP, c = e % NP;
+    sS[r * LD + c] = (r < NC && c < NC) ? 0.5 * (T1[r * NC + c] + T1[c * NC + r]) : 0.0;
+  }
+  // 2. gauge generators
+  for (int e = tid; e < NP * 8; e += blockDim.x) {
+    const int r = e >> 3, k = e & 7;
+    double v = 0.0;
+    if (r < NC && k < 7) {
+      const double* cm = cams + (r / 6) * ACS_CAM_STRIDE;
+      const int i = r % 6;
+      if (i < 3)
+        v = k < 3 ? -cm[8 + 3 * i + k] : 0.0;
+      else
+        v = k < 3 ? 0.0 : (k < 6 ? -cm[8 + 3 * (i - 3) + (k - 3)] : cm[17 + (i - 3)]);
+    }
+    sQ[e] = v;
+  }
+  __syncthreads();
+  // 3. wave 0: two-pass Gram-Schmidt (lane l owns rows l and l + 64) and mu = max diag S
+  if (tid < 64) {
+    const int r0 = tid, r1 = tid + 64;
+    const bool h0 = r0 < NC, h1 = r1 < NC;  // rows past NC are not this lane's to touch
+    int gbad = 0;
+    for (int k = 0; k < 7; ++k) {
+      double x0 = h0 ? sQ[r0 * 8 + k] : 0.0, x1 = h1 ? sQ[r1 * 8 + k] : 0.0;
+      const double n0 = sqrt(wave_sum64(x0 * x0 + x1 * x1));
+      for (int pass = 0; pass < 2; ++pass)
+        for (int j = 0; j < k; ++j) {
+          const double q0 = h0 ? sQ[r0 * 8 + j] : 0.0, q1 = h1 ? sQ[r1 * 8 + j] : 0.0;
+          const double dot = wave_sum64(q0 * x0 + q1 * x1);
+          x0 -= dot * q0;
+          x1 -= dot * q1;
+        }
+      const double n1 = sqrt(wave_sum64(x0 * x0 + x1 * x1));
+      const bool ok = n1 > 1e-8 * n0;  // a column in the span of the earlier ones: rank < 7
+      const double inv = ok ? 1.0 / n1 : 0.0;
+      gbad |= ok ? 0 : 1;
+      if (h0) sQ[r0 * 8 + k] = x0 * inv;
+      if (h1) sQ[r1 * 8 + k] = x1 * inv;
+    }
+    double mu = h0 ? sS[r0 * LD + r0] : 0.0;
+    if (h1) mu = fmax(mu, sS[r1 * LD + r1]);
+    for (int m = 32; m > 0; m >>= 1) mu = fmax(mu, __shfl_xor(mu, m, 64));
+    if (tid == 0) {
+      s_sm[0] = (double)gbad;
+      s_sm[1] = mu > 0.0 ? mu : 1.0;
+      s_sm[2] = 0.0;
+    }
+  }
+  __syncthreads();
+  const double mu = s_sm[1];
+  // 4. A = S + mu Q Q^T, scaled to unit diagonal (a diagonal entry that is not > 0 zeroes its row
+  //    and column, which the pivot test then fails)
+  for (int r = tid; r < NP; r += blockDim.x) {
+    double sc = 1.0;
+    if (r < NC) {
+      double qq = 0.0;
+      for (int k = 0; k < 7; ++k) qq += sQ[r * 8 + k] * sQ[r * 8 + k];
+      const double dd = sS[r * LD + r] + mu * qq;
+      sc = dd > 0.0 ? 1.0 / sqrt(dd) : 0.0;
+    }
+    ssc[r] = sc;
+  }
+  __syncthreads();
+  for (int e = tid; e < NP * NP; e += blockDim.x) {
+    const int r = e / NP, c = e % NP;
+    double v = r == c ? 1.0 : 0.0;
+    if (r < NC && c < NC) {
+      double qq = 0.0;
+      for (int k = 0; k < 7; ++k) qq += sQ[r * 8 + k] * sQ[c * 8 + k];
+      v = (sS[r * LD + c] + mu * qq) * ssc[r] * ssc[c];
+    }
+    sS[r * LD + c] = v;
+    Ag[e] = v;  // kept for the inverse and its refinement
+  }
+  __syncthreads();
+  // 5. pivot test: scalar right-looking LDL^T of Ah in natural order, in place (Ah is reloaded)
+  double minp = __builtin_inf();
+  bool pbad = false;
+  for (int k = 0; k < NC; ++k) {
+    const double dk = sS[k * LD + k];  // uniform
+    if (!(dk > XC_PIVOT_TOL)) {        // a NaN fails
+      pbad = true;
+      minp = dk < minp ? dk : (dk != dk ? dk : minp);
+      break;
+    }
+    minp = fmin(minp, dk);
+    const double inv = 1.0 / dk;
+    const int m = NC - k - 1;
+    for (int e = tid; e < m * m; e += blockDim.x) {
+      const int i = k + 1 + e / m, j = k + 1 + e % m;
+      sS[i * LD + j] -= sS[i * LD + k] * inv * sS[k * LD + j];
+    }
+    __syncthreads();
+  }
+  __syncthreads();
+  const bool gbad = s_sm[0] != 0.0;
+  bool degenerate = pbad || gbad;  // uniform
+  if (!degenerate) {
+    // 6. SPD inverse on the MFMA tiles
+    for (int e = tid; e < NP * NP; e += blockDim.x) sS[(e / NP) * LD + e % NP] = Ag[e];
+    __syncthreads();
+    wg_spd_inverse(sS, LD, NP >> 4, tmp, bad);
+    // 7. one refinement step X <- X + X (I - Ah X)
+    wg_mgemm<false, false>(T1, NP, Ag, NP, sS, LD, NP, NP, NP, -1.0, 0.0);
+    for (int r = tid; r < NP; r += blockDim.x) T1[r * NP + r] += 1.0;
+    __syncthreads();
+    wg_mgemm<false, false>(T2, NP, sS, LD, T1, NP, NP, NP, NP, 1.0, 0.0);
+    for (int e = tid; e < NP * NP; e += blockDim.x) sS[(e / NP) * LD + e % NP] += T2[e];
+    __syncthreads();
+    // 8. unscale, minus Q Q^T / mu
+    const double imu = 1.0 / mu;
+    for (int e = tid; e < nE; e += blockDim.x) {
+      const int r = e / NC, c = e % NC;
+      double qq = 0.0;
+      for (int k = 0; k < 7; ++k) qq += sQ[r * 8 + k] * sQ[c * 8 + k];
+      sS[r * LD + c] = sS[r * LD + c] * ssc[r] * ssc[c] - qq * imu;
+    }
+    __syncthreads();
+    if (ar.gauge == ACS_GAUGE_ANCHOR) {
+      // 9. M <- P M P^T, P = I - K Cm, K = Q (Cm Q)^-1
+      if (tid == 0) {
+        const double* ca = cams + ar.a * ACS_CAM_STRIDE;
+        const double* cb = cams + ar.b * ACS_CAM_STRIDE;
+        double e3[3], n2 = 0.0;
+        for (int j = 0; j < 3; ++j) {  // c = -R^T t
+          const double a_ = -(ca[8 + j] * ca[17] + ca[11 + j] * ca[18] + ca[14 + j] * ca[19]);
+          const double b_ = -(cb[8 + j] * cb[17] + cb[11 + j] * cb[18] + cb[14 + j] * cb[19]);
+          e3[j] = b_ - a_;
+          n2 += e3[j] * e3[j];
+        }
+        const double in = 1.0 / sqrt(n2);
+        for (int j = 0; j < 3; ++j) e3[j] *= in;
+        // y = R_b e; h = [t_b x y, -y]  (e^T (-R^T [t]x) = -y^T [t]x = (t x y)^T)
+        double y[3];
+        for (int i = 0; i < 3; ++i) y[i] = cb[8 + 3 * i] * e3[0] + cb[8 + 3 * i + 1] * e3[1] + cb[8 + 3 * i + 2] * e3[2];
+        const double* tb = cb + 17;
+        double* h = s_sm + 8;
+        h[0] = tb[1] * y[2] - tb[2] * y[1];
+        h[1] = tb[2] * y[0] - tb[0] * y[2];
+        h[2] = tb[0] * y[1] - tb[1] * y[0];
+        h[3] = -y[0];
+        h[4] = -y[1];
+        h[5] = -y[2];
+        // Cm Q (7 x 7) and its inverse by Gauss-Jordan with partial pivoting
+        double A[7][14];
+        for (int k = 0; k < 7; ++k) {
+          for (int i = 0; i < 6; ++i) A[i][k] = sQ[(6 * ar.a + i) * 8 + k];
+          double v = 0.0;
+          for (int j = 0; j < 6; ++j) v += h[j] * sQ[(6 * ar.b + j) * 8 + k];
+          A[6][k] = v;
+          for (int i = 0; i < 7; ++i) A[i][7 + k] = i == k ? 1.0 : 0.0;
+        }
+        bool abad = false;
+        for (int k = 0; k < 7; ++k) {
+          int pv = k;
+          for (int i = k + 1; i < 7; ++i)
+            if (fabs(A[i][k]) > fabs(A[pv][k])) pv = i;
+          if (!(fabs(A[pv][k]) > 1e-12)) {
+            abad = true;
+            break;
+          }
+          for (int j = 0; j < 14; ++j) {
+            const double x = A[k][j];
+            A[k][j] = A[pv][j];
+            A[pv][j] = x;
+          }
+          const double ip = 1.0 / A[k][k];
+          for (int j = 0; j < 14; ++j) A[k][j] *= ip;
+          for (int i = 0; i < 7; ++i) {
+            if (i == k) continue;
+            const double f = A[i][k];
+            for (int j = 0; j < 14; ++j) A[i][j] -= f * A[k][j];
+          }
+        }
+        for (int i = 0; i < 7; ++i)
+          for (int k = 0; k < 7; ++k) s_sm[16 + i * 7 + k] = A[i][7 + k];
+        s_sm[2] = abad ? 1.0 : 0.0;
+      }
+      __syncthreads();
+      const double* h = s_sm + 8;
+      for (int e = tid; e < NC * 8; e += blockDim.x) {
+        const int r = e >> 3, k = e & 7;
+        double v = 0.0;
+        if (k < 7)
+          for (int j = 0; j < 7; ++j) v += sQ[r * 8 + j] * s_sm[16 + j * 7 + k];
+        sK[e] = v;
+      }
+      for (int e = tid; e < 7 * NC; e += blockDim.x) {
+        const int k = e / NC, c = e % NC;
+        double v;
+        if (k < 6) {
+          v = sS[(6 * ar.a + k) * LD + c];
+        } else {
+          v = 0.0;
+          for (int j = 0; j < 6; ++j) v += h[j] * sS[(6 * ar.b + j) * LD + c];
+        }
+        sCM[k * NP + c] = v;
+      }
+      __syncthreads();
+      for (int e = tid; e < nE; e += blockDim.x) {
+        const int r = e / NC, c = e % NC;
+        double v = 0.0;
+        for (int k = 0; k < 7; ++k) v += sK[r * 8 + k] * sCM[k * NP + c];
+        sS[r * LD + c] -= v;
+      }
+      __syncthreads();
+      for (int e = tid; e < NC * 8; e += blockDim.x) {
+        const int r = e >> 3, k = e & 7;
+        double v = 0.0;
+        if (k < 6) {
+          v = sS[r * LD + 6 * ar.a + k];
+        } else if (k == 6) {
+          for (int j = 0; j < 6; ++j) v += h[j] * sS[r * LD + 6 * ar.b + j];
+        }
+        sMC[e] = v;
+      }
+      __syncthreads();
+      for (int e = tid; e < nE; e += blockDim.x) {
+        const int r = e / NC, c = e % NC;
+        double v = 0.0;
+        for (int k = 0; k < 7; ++k) v += sMC[r * 8 + k] * sK[c * 8 + k];
+        sS[r * LD + c] -= v;
+      }
+      __syncthreads();
+      degenerate = s_sm[2] != 0.0;
+    }
+  }
+  // 10. mirror the upper triangle, sigma^2, exact zeros on the anchor camera, NaN when degenerate
+  const double nan = __builtin_nan("");
+  const bool anchored = ar.gauge == ACS_GAUGE_ANCHOR;
+  for (int e = tid; e < nE; e += blockDim.x) {
+    const int r = e / NC, c = e % NC, lo = min(r, c), hi = max(r, c);
+    double v = ar.s2 * sS[lo * LD + hi];
+    if (anchored && (r / 6 == ar.a || c / 6 == ar.a)) v = 0.0;
+    cov[e] = degenerate ? nan : v;
+  }
+  // the report: sd extremes and the point sums, fixed-order trees
+  double rs = 0.0, ts = 0.0, sw = 0.0;
+  long long cnt[3] = {0, 0, 0}, m = 0;
+  for (int r = tid; r < NC; r += blockDim.x) {
+    double v = ar.s2 * sS[r * LD + r];
+    if (anchored && r / 6 == ar.a) v = 0.0;
+    const double sd = sqrt(v);
+    if (r % 6 < 3)
+      rs = fmax(rs, sd);
+    else
+      ts = fmax(ts, sd);
+  }
+  for (int i = tid; i < d.n; i += blockDim.x) {
+    const int s = status[i];
+    if (s >= 0 && s < 3) cnt[s]++;
+    sw += wr2[i];
+    m += nres[i];
+  }
+  __syncthreads();
+  double* rd = tmp;                         // 256 x 2: sum w r^2 and the rotation sd maximum
+  long long* ri = (long long*)(s_sm + 128);  // 256 x 4
+  rd[tid] = sw;
+  rd[256 + tid] = rs;
+  s_red[tid] = ts;
+  for (int k = 0; k < 3; ++k) ri[tid * 4 + k] = cnt[k];
+  ri[tid * 4 + 3] = m;
+  __syncthreads();
+  for (int h = 128; h > 0; h >>= 1) {
+    if (tid < h) {
+      rd[tid] += rd[tid + h];
+      rd[256 + tid] = fmax(rd[256 + tid], rd[256 + tid + h]);
+      s_red[tid] = fmax(s_red[tid], s_red[tid + h]);
+      for (int k = 0; k < 4; ++k) ri[tid * 4 + k] += ri[(tid + h) * 4 + k];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    const long long n_ok = ri[0], dof = ri[3] - 3 * n_ok - (6 * d.C - 7);
+    rep->status = degenerate ? ACS_EXT_COV_DEGENERATE : ACS_EXT_COV_OK;
+    rep->reserved = 0;
+    rep->n_points = d.n;
+    rep->n_ok = n_ok;
+    rep->n_noobs = ri[1];
+    rep->n_degenerate = ri[2];
+    rep->dof = dof;
+    rep->min_pivot = gbad ? 0.0 : minp;
+    rep->sigma_hat_px = dof > 0 ? sqrt(rd[0] / (double)dof) : nan;
+    rep->rot_sd_max = degenerate ? nan : rd[256];
+    rep->trans_sd_max = degenerate ? nan : s_red[0];
+  }
+}
+
+// The throughput path: one point per aligned lane group, lane l owns slot l. cov_cc (6C x 6C,
+// sigma^2 applied) is staged in LDS.
+template <int G>
+__global__ __launch_bounds__(256) void k_extcov_points(XcDims d, const double* __restrict__ covc,
+                                                       const double* __restrict__ Q, const double* __restrict__ Vi,
+                                                       const int32_t* __restrict__ status,
+                                                       const uint8_t* __restrict__ mask,
+                                                       const uint8_t* __restrict__ camid, double s2,
+                                                       const acs_sba_ext_cov_report* __restrict__ rep,
+                                                       double* __restrict__ covp) {
+  const int NC = 6 * d.C;
+  extern __shared__ double s_cc[];
+  for (int i = threadIdx.x; i < NC * NC; i += blockDim.x) s_cc[i] = covc[i];
+  __syncthreads();
+  const int lane = threadIdx.x & (G - 1);
+  const int64_t p = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / G;
+  if (p >= d.n) return;  // whole group leaves together
+  const bool pok = status[p] == ACS_COV_OK;
+  double acc[6] = {0, 0, 0, 0, 0, 0};  // B^T cov_cc B, packed upper
+  if (pok) {
+    for (int slot = lane; slot < d.K; slot += G) {
+      const int64_t o = p * d.K + slot;
+      if (!mask[o] || camid[o] >= d.C) continue;
+      const int co = camid[o];
+      const double* Wo = Q + (size_t)o * XC_Q + 21;
+      double T[18];
+      for (int e = 0; e < 18; ++e) T[e] = 0.0;
+      for (int s = 0; s < d.K; ++s) {
+        const int64_t o2 = p * d.K + s;
+        if (!mask[o2] || camid[o2] >= d.C) continue;
+        const double* W2 = Q + (size_t)o2 * XC_Q + 21;
+        const double* blk = s_cc + (size_t)(6 * co) * NC + 6 * camid[o2];
+        for (int k = 0; k < 6; ++k) {
+          const double w0 = W2[k * 3], w1 = W2[k * 3 + 1], w2 = W2[k * 3 + 2];
+          for (int i = 0; i < 6; ++i) {
+            const double c = blk[i * NC + k];
+            T[i * 3] += c * w0;
+            T[i * 3 + 1] += c * w1;
+            T[i * 3 + 2] += c * w2;
+          }
+        }
+      }
+      for (int i = 0; i < 6; ++i) {
+        const double w0 = Wo[i * 3], w1 = Wo[i * 3 + 1], w2 = Wo[i * 3 + 2];
+        acc[0] += w0 * T[i * 3];
+        acc[1] += w0 * T[i * 3 + 1];
+        acc[2] += w0 * T[i * 3 + 2];
+        acc[3] += w1 * T[i * 3 + 1];
+        acc[4] += w1 * T[i * 3 + 2];
+        acc[5] += w2 * T[i * 3 + 2];
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 6; ++i) acc[i] = group_sum<G>(acc[i]);
+  if (lane != 0) return;
+  const double* vi = Vi + (size_t)p * 6;
+  const double A[9] = {vi[0], vi[1], vi[2], vi[1], vi[3], vi[4], vi[2], vi[4], vi[5]};
+  const double Mm[9] = {acc[0], acc[1], acc[2], acc[1], acc[3], acc[4], acc[2], acc[4], acc[5]};
+  double AM[9];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) AM[i * 3 + j] = A[i * 3] * Mm[j] + A[i * 3 + 1] * Mm[3 + j] + A[i * 3 + 2] * Mm[6 + j];
+  const bool good = pok && rep->status == ACS_EXT_COV_OK;
+  const double nan = __builtin_nan("");
+  double out[9];
+  for (int i = 0; i < 3; ++i)
+    for (int j = i; j < 3; ++j) {
+      const double v = s2 * A[i * 3 + j] + AM[i * 3] * A[j] + AM[i * 3 + 1] * A[3 + j] + AM[i * 3 + 2] * A[6 + j];
+      out[i * 3 + j] = out[j * 3 + i] = good ? v : nan;  // the upper triangle mirrored
+    }
+  double* c = covp + 9 * p;
+  for (int e = 0; e < 9; ++e) c[e] = out[e];
+}
+
+#define XC_G_SWITCH(G, CALL) \
+  switch (G) {               \
+    case 2: CALL(2); break;  \
+    case 4: CALL(4); break;  \
+    case 8: CALL(8); break;  \
+    case 16: CALL(16); break; \
+    case 32: CALL(32); break; \
+    default: CALL(64); break; \
+  }
+
+extern "C" {
+
+void acs_sba_ext_cov_default_opts(acs_sba_ext_cov_opts* o) {
+  o->gauge = ACS_GAUGE_ANCHOR;
+  o->anchor_cam = 0;
+  o->scale_cam = 1;
+  o->reserved = 0;
+  o->f_scale = 1.0;
+  o->sigma_px = 1.0;
+}
+
+int acs_sba_extrinsics_covariance(acs_ctx* ctx, const double* cams, int32_t n_cams, const double* uv,
+                                  const int32_t* pt_idx, const int32_t* cam_idx, int64_t n_obs, const double* pts,
+                                  int64_t n_pts, const acs_sba_ext_cov_opts* opts, double* cov_cams, double* cov_pts,
+                                  int32_t* pt_status, acs_sba_ext_cov_report* report, uint32_t flags) {
+  ACS_DEVICE_GUARD(ctx);
+  ACS_FISHEYE_ONLY(ctx, flags, "acs_sba_extrinsics_covariance");
+  acs_sba_ext_cov_opts op;
+  acs_sba_ext_cov_default_opts(&op);
+  if (opts) op = *opts;
+  ACS_CHECK(ctx, n_cams >= 1 && n_cams <= EXT_MAXC, "acs_sba_extrinsics_covariance: n_cams=%d (1..%d)", n_cams,
+            EXT_MAXC);
+  ACS_CHECK(ctx, n_obs >= 1 && n_pts >= 1 && n_obs < (int64_t)INT32_MAX && n_pts < (int64_t)INT32_MAX / 64,
+            "acs_sba_extrinsics_covariance: bad sizes");
+  ACS_CHECK(ctx, op.f_scale > 0 && op.sigma_px > 0, "acs_sba_extrinsics_covariance: f_scale=%g sigma_px=%g (both > 0)",
+            op.f_scale, op.sigma_px);
+  ACS_CHECK(ctx, op.gauge == ACS_GAUGE_FREE || op.gauge == ACS_GAUGE_ANCHOR, "acs_sba_extrinsics_covariance: gauge %d",
+            op.gauge);
+  ACS_CHECK(ctx, cams && uv && pt_idx && cam_idx && pts && cov_cams, "acs_sba_extrinsics_covariance: null argument");
+  hipStream_t s = ctx->stream;
+  // one camera has no anchor pair: the problem is reported DEGENERATE, not refused
+  const bool anchored = op.gauge == ACS_GAUGE_ANCHOR && n_cams >= 2;
+  if (anchored) {
+    ACS_CHECK(ctx, op.anchor_cam >= 0 && op.anchor_cam < n_cams && op.scale_cam >= 0 && op.scale_cam < n_cams,
+              "acs_sba_extrinsics_covariance: anchor_cam=%d scale_cam=%d (0..%d)", op.anchor_cam, op.scale_cam,
+              n_cams - 1);
+    ACS_CHECK(ctx, op.anchor_cam != op.scale_cam, "acs_sba_extrinsics_covariance: anchor_cam == scale_cam (%d)",
+              op.anchor_cam);
+    double rec[2][ACS_CAM_STRIDE];
+    const int id[2] = {op.anchor_cam, op.scale_cam};
+    for (int k = 0; k < 2; ++k) {
+      const double* src = cams + (size_t)id[k] * ACS_CAM_STRIDE;
+      if (flags & ACS_DEVICE_PTRS) {
+        ACS_HIP(ctx, hipMemcpyAsync(rec[k], src, sizeof(rec[k]), hipMemcpyDeviceToHost, s));
+        ACS_HIP(ctx, hipStreamSynchronize(s));
+      } else {
+        std::memcpy(rec[k], src, sizeof(rec[k]));
+      }
+    }
+    double d2 = 0.0, sc2 = 0.0;
+    for (int j = 0; j < 3; ++j) {
+      double c[2];
+      for (int k = 0; k < 2; ++k)
+        c[k] = -(rec[k][8 + j] * rec[k][17] + rec[k][11 + j] * rec[k][18] + rec[k][14 + j] * rec[k][19]);
+      d2 += (c[1] - c[0]) * (c[1] - c[0]);
+      sc2 += c[0] * c[0] + c[1] * c[1];
+    }
+    ACS_CHECK(ctx, d2 > 1e-24 * (sc2 > 1.0 ? sc2 : 1.0),
+              "acs_sba_extrinsics_covariance: the centres of cameras %d and %d coincide", op.anchor_cam, op.scale_cam);
+  }
+  void *dcam, *duv, *dpi, *dci, *dp;
+  int rc;
+  if ((rc = acs_stage_in(ctx, WS_CAMS, cams, sizeof(double) * ACS_CAM_STRIDE * n_cams, flags, &dcam))) return rc;
+  if ((rc = acs_stage_in(ctx, WS_UV, uv, sizeof(double) * 2 * n_obs, flags, &duv))) return rc;
+  if ((rc = acs_stage_in(ctx, WS_PTIDX, pt_idx, sizeof(int32_t) * n_obs, flags, &dpi))) return rc;
+  if ((rc = acs_stage_in(ctx, WS_CAMIDX, cam_idx, sizeof(int32_t) * n_obs, flags, &dci))) return rc;
+  if ((rc = acs_stage_in(ctx, WS_PTS, pts, sizeof(double) * 3 * n_pts, flags, &dp))) return rc;
+  double2* uvp;
+  uint8_t *mk, *cid;
+  int K;
+  if ((rc = acs_obs_to_slots(ctx, (const double*)duv, (const int32_t*)dpi, (const int32_t*)dci, n_obs, n_pts, n_cams,
+                             &uvp, &mk, &cid, &K))) {
+    // the shared slot builder words its errors for acs_sba_points: name this entry point
+    ctx->err = "acs_sba_extrinsics_covariance: " + ctx->err;
+    return rc;
+  }
+  ACS_CHECK(ctx, K <= 64, "acs_sba_extrinsics_covariance: a point has %d observations (max 64)", K);
+  XcDims d{(int)n_pts, K, n_cams, ext_chunk_points(K), op.f_scale * op.f_scale};
+  int G = 2;
+  while (G < K) G <<= 1;
+  const int nchunk = (int)((n_pts + d.chunk - 1) / d.chunk);
+  const int NC = 6 * n_cams, NP = ((NC + 15) / 16) * 16, nE = NC * NC;
+  size_t off = 0;
+  auto take = [&](size_t cnt) {
+    size_t o = off;
+    off += ((cnt * sizeof(double) + 255) / 256) * 256 / sizeof(double);
+    return o;
+  };
+  const size_t oQ = take((size_t)n_pts * K * XC_Q), oV = take((size_t)n_pts * 6), oW = take(n_pts),
+               oN = take(((size_t)n_pts + 1) / 2), oPart = take((size_t)nchunk * nE), oA = take((size_t)NP * NP),
+               oT1 = take((size_t)NP * NP), oT2 = take((size_t)NP * NP), obad = take(2);
+  double* arena = (double*)acs_ws(ctx, WS_FTE7, off * sizeof(double));
+  double* dcc = (double*)acs_out_buf(ctx, WS_OUT0, cov_cams, sizeof(double) * nE, flags);
+  // without cov_pts the point kernel is not run; the status is needed by the camera kernel anyway
+  double* dcp = cov_pts ? (double*)acs_out_buf(ctx, WS_OUT1, cov_pts, sizeof(double) * 9 * n_pts, flags) : nullptr;
+  int32_t* dst = (int32_t*)acs_out_buf(ctx, WS_PERPT_I, pt_status, sizeof(int32_t) * n_pts,
+                                       pt_status ? flags : (flags & ~ACS_DEVICE_PTRS));
+  acs_sba_ext_cov_report* drep = (acs_sba_ext_cov_report*)acs_ws(ctx, WS_REPORT, sizeof(acs_sba_ext_cov_report));
+  if (!arena || !dcc || (cov_pts && !dcp) || !dst || !drep) return ACS_E_NOMEM;
+  double *Q = arena + oQ, *Vi = arena + oV, *wr2 = arena + oW, *part = arena + oPart, *Ag = arena + oA,
+         *T1 = arena + oT1, *T2 = arena + oT2;
+  int32_t* nres = (int32_t*)(arena + oN);
+  int* bad = (int*)(arena + obad);
+  ACS_HIP(ctx, hipMemsetAsync(bad, 0, sizeof(int), s));
+  const int blocks = acs_grid((int64_t)n_pts * G, 256);
+#define XC_LIN(g)                                                                                              \
+  hipLaunchKernelGGL((k_extcov_linearize<g>), dim3(blocks), dim3(256), 0, s, d, (const double*)dcam,           \
+                     (const double*)dp, (const double2*)uvp, (const uint8_t*)mk, (const uint8_t*)cid, Q, Vi, dst, \
+                     wr2, nres)
+  XC_G_SWITCH(G, XC_LIN)
+#undef XC_LIN
+  const size_t lds_schur = sizeof(double) * (size_t)d.chunk * K * 18 + sizeof(int) * (size_t)d.chunk * K;
+  hipLaunchKernelGGL(k_extcov_schur, dim3(nchunk), dim3(256), lds_schur, s, d, (const double*)Q, (const double*)Vi,
+                     (const int32_t*)dst, (const uint8_t*)mk, (const uint8_t*)cid, part);
+  XcCamArgs ar{nchunk, anchored ? ACS_GAUGE_ANCHOR : ACS_GAUGE_FREE, anchored ? op.anchor_cam : 0,
+               anchored ? op.scale_cam : 0, op.sigma_px * op.sigma_px};
+  hipLaunchKernelGGL(k_extcov_cams, dim3(1), dim3(256), extcov_cams_lds(NP), s, d, ar, (const double*)part,
+                     (const double*)dcam, (const int32_t*)dst, (const double*)wr2, (const int32_t*)nres, Ag, T1, T2,
+                     dcc, drep, bad);
+  if (dcp) {
+#define XC_PTS(g)                                                                                                  \
+  hipLaunchKernelGGL((k_extcov_points<g>), dim3(blocks), dim3(256), sizeof(double) * nE, s, d, (const double*)dcc, \
+                     (const double*)Q, (const double*)Vi, (const int32_t*)dst, (const uint8_t*)mk,                  \
+                     (const uint8_t*)cid, ar.s2, (const acs_sba_ext_cov_report*)drep, dcp)
+    XC_G_SWITCH(G, XC_PTS)
+#undef XC_PTS
+  }
+  ACS_HIP(ctx, hipGetLastError());
+  if ((rc = acs_stage_out(ctx, cov_cams, dcc, sizeof(double) * nE, flags))) return rc;
+  if (cov_pts && (rc = acs_stage_out(ctx, cov_pts, dcp, sizeof(double) * 9 * n_pts, flags))) return rc;
+  if (pt_status && (rc = acs_stage_out(ctx, pt_status, dst, sizeof(int32_t) * n_pts, flags))) return rc;
+  if (report) ACS_HIP(ctx, hipMemcpyAsync(report, drep, sizeof(*report), hipMemcpyDeviceToHost, s));
+  ACS_HIP(ctx, hipStreamSynchronize(s));
+  return ACS_OK;
+}
+
+}  // extern "C"

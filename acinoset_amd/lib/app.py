@@ -26,9 +26,12 @@ def sba_points_fisheye(scene_fpath, points_2d_df, covariance=False, sigma_px=1.0
 
 
 def sba_board_points_fisheye(scene_fpath, points_fpaths, out_fpath, manual_points_fpath=None, manual_points_only=False,
-                             camera_indices=None):
+                             camera_indices=None, covariance=False, sigma_px=1.0):
+    """`covariance=True` also writes `<out_fpath stem>_cov.json` (see `_sba_board_points`); the
+    scene JSON at out_fpath is the same file either way."""
     return _sba_board_points(scene_fpath, points_fpaths, manual_points_fpath, out_fpath, triangulate_points_fisheye,
-                             project_points_fisheye, camera_indices, manual_points_only)
+                             project_points_fisheye, camera_indices, manual_points_only, covariance=covariance,
+                             sigma_px=sigma_px)
 
 
 def _gaze_targets(head_pos, nose_pos, r_eye_pos, r=3.0):

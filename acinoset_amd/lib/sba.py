@@ -12,6 +12,8 @@
   and `_sba_board_points`, with every image's first-two-camera triangulation batched into one
   GPU call (acs_triangulate_pairs) and the joint points + extrinsics solve on the GPU.
 """
+import json
+import os
 from time import time
 
 import numpy as np
@@ -175,14 +177,48 @@ def cost_func_points_extrinsics(params, n_cams, n_points, point_3d_indices, came
                                  points_2d, project_func)
 
 
+def camera_centres(r_arr, t_arr):
+    """World-frame camera centres c = -R^T t, (C, 3)."""
+    R = np.asarray(r_arr, np.float64).reshape(-1, 3, 3)
+    t = np.asarray(t_arr, np.float64).reshape(-1, 3)
+    return -np.einsum('cji,cj->ci', R, t)
+
+
+def default_anchor(r_arr, t_arr):
+    """The default anchor pair of the pose covariance: camera 0 and the camera whose centre is
+    farthest from it (the lowest index on ties)."""
+    c = camera_centres(r_arr, t_arr)
+    return 0, int(np.argmax(np.linalg.norm(c - c[0], axis=1)))
+
+
+def camera_centre_covariance(cov_block, r, t):
+    """Covariance (3, 3, m^2) of a camera's centre c = -R^T t in world coordinates from its pose
+    block (6, 6) over (dw, dt) with R <- exp([dw]x) R, t <- t + dt: J cov J^T with
+    J = dc/d(dw, dt) = [-R^T [t]x | -R^T]."""
+    R = np.asarray(r, np.float64).reshape(3, 3)
+    t = np.asarray(t, np.float64).reshape(3)
+    tx = np.array([[0, -t[2], t[1]], [t[2], 0, -t[0]], [-t[1], t[0], 0]])
+    J = np.concatenate([-R.T @ tx, -R.T], 1)
+    return J @ np.asarray(cov_block, np.float64).reshape(6, 6) @ J.T
+
+
 def bundle_adjust_points_and_extrinsics(points_2d, points_3d, point_3d_indices, camera_indices, k_arr, d_arr, r_arr,
-                                        t_arr, project_func=None, f_scale=1.0, **opts):
+                                        t_arr, project_func=None, f_scale=1.0, covariance=False, sigma_px=1.0,
+                                        gauge='anchor', anchor=None, **opts):
     """`src/lib/sba.py:158-178` -> acs_sba_extrinsics: points and every camera's rotation and
     translation refined together (intrinsics fixed) on the same Cauchy objective (scipy's
     default f_scale = 1). Returns (obj_pts (n,3), r_arr (C,3,3), t_arr (C,3,1),
     {'before', 'after'}) like the reference; rotations stay orthonormal matrices (updated
     on SO(3), which is what the reference's Rodrigues round trip represents).
-    Fisheye model only: `project_func=calib.project_points` raises NotImplementedError."""
+    Fisheye model only: `project_func=calib.project_points` raises NotImplementedError.
+    `covariance=True` adds to the returned dict, evaluated at the returned solution with the same
+    f_scale and the pixel noise `sigma_px` (acs_sba_extrinsics_covariance): `cov_cams` (6C, 6C),
+    camera c's (dw, dt) at rows 6c..6c+5 with R <- exp([dw]x) R (rad) and t <- t + dt (m);
+    `cov_cam_blocks` (C, 6, 6), its diagonal blocks; `cov_points` (n, 3, 3), the joint point
+    covariances; `cov_status` (n,) and `cov_report` (with 'gauge' and 'anchor'). gauge 'anchor'
+    holds camera anchor[0]'s pose and the distance between the centres of anchor[0] and anchor[1]
+    (default: default_anchor of the solution); 'free' is the inner-constraint gauge. The points,
+    cameras and residuals are those of the plain call."""
     if is_standard_model(project_func):
         raise NotImplementedError('bundle_adjust_points_and_extrinsics: the standard camera model is built for the '
                                   'points-only SBA only (the joint solve would silently use the fisheye model)')
@@ -199,7 +235,20 @@ def bundle_adjust_points_and_extrinsics(points_2d, points_3d, point_3d_indices, 
     print(f'\nOptimization took {t1 - t0:.2f} seconds')
     r_out = cams[:, 8:17].reshape(n, 3, 3).copy()
     t_out = cams[:, 17:20].reshape(n, 3, 1).copy()
-    return pts, r_out, t_out, dict(before=rb, after=ra)
+    res = dict(before=rb, after=ra)
+    if covariance:
+        pair = default_anchor(r_out, t_out) if anchor is None else (int(anchor[0]), int(anchor[1]))
+        cc, cp, cst, crep = ctx.sba_extrinsics_covariance(cams, np.asarray(points_2d, np.float64),
+                                                          np.asarray(point_3d_indices), np.asarray(camera_indices),
+                                                          pts, f_scale=float(f_scale), sigma_px=float(sigma_px),
+                                                          gauge=gauge, anchor=pair)
+        crep.update(gauge=gauge, anchor=pair if gauge == 'anchor' else None)
+        print(f'GPU SBA pose covariance ({gauge}): {crep["status_name"]}, rotation sd <= {crep["rot_sd_max"]:.3e} rad, '
+              f'translation sd <= {crep["trans_sd_max"]:.3e} m; sigma_hat {crep["sigma_hat_px"]:.4f} px (sigma_px '
+              f'{float(sigma_px):g})')
+        blocks = np.stack([cc[6 * c:6 * c + 6, 6 * c:6 * c + 6] for c in range(n)])
+        res.update(cov_cams=cc, cov_cam_blocks=blocks, cov_points=cp, cov_status=cst, cov_report=crep)
+    return pts, r_out, t_out, res
 
 
 # ---- calibration-board front end (src/lib/sba.py:37-137, :196-282) -----------------------
@@ -301,9 +350,14 @@ def bundle_adjust_board_points_only(img_pts_arr, fnames_arr, board_shape, k_arr,
 
 
 def _sba_board_points(scene_fpath, points_fpaths, manual_points_fpath, out_fpath, triangulate_func=None,
-                      project_func=None, camera_indices=None, manual_points_only=False):
+                      project_func=None, camera_indices=None, manual_points_only=False, covariance=False,
+                      sigma_px=1.0):
     """`src/lib/sba.py:209-282`: board corners (+ optional hand-labelled points) -> joint
     points + extrinsics SBA -> refined scene JSON at out_fpath. Returns the residuals.
+    `covariance=True` also writes `<out_fpath stem>_cov.json` beside it: the gauge and anchor
+    pair, the per-camera 6 x 6 pose blocks over (dw, dt), the rotation (rad) and translation (m)
+    sds, the covariance of every camera centre in world coordinates, sigma_hat_px and the
+    status; the scene JSON is byte-equal to the plain call's.
 
     Kept as the reference has it: manual point indices are offset by the LAST board point
     index (`manual + board.max()`, :249), so the first manual point shares its index with
@@ -338,8 +392,32 @@ def _sba_board_points(scene_fpath, points_fpaths, manual_points_fpath, out_fpath
         p2, p3, pi, ci = prepare_calib_board_data_for_bundle_adjustment(img_pts_arr, fnames_arr, board_shape, k_arr,
                                                                         d_arr, r_arr, t_arr, triangulate_func)
     obj_pts, r_arr, t_arr, res = bundle_adjust_points_and_extrinsics(p2, p3, pi, ci, k_arr, d_arr, r_arr, t_arr,
-                                                                     project_func)
+                                                                     project_func, covariance=covariance,
+                                                                     sigma_px=sigma_px)
     print(f"\nBefore: mean: {np.mean(res['before'])}, std: {np.std(res['before'])}")
     print(f"After: mean: {np.mean(res['after'])}, std: {np.std(res['after'])}\n")
     save_scene(out_fpath, k_arr, d_arr, r_arr, t_arr, cam_res)
+    if covariance:
+        save_pose_covariance(os.path.splitext(out_fpath)[0] + '_cov.json', res, r_arr, t_arr, sigma_px)
     return res
+
+
+def save_pose_covariance(fpath, res, r_arr, t_arr, sigma_px):
+    """The `_cov.json` sibling of a refined scene file, from the residual dict of
+    bundle_adjust_points_and_extrinsics(covariance=True)."""
+    rep = res['cov_report']
+    blocks = np.asarray(res['cov_cam_blocks'])
+    sd = np.sqrt(np.diagonal(blocks, axis1=1, axis2=2))
+
+    def lst(a):  # NaN (a degenerate problem) is not JSON: null
+        return [lst(x) for x in a] if np.ndim(a) else (None if np.isnan(a) else float(a))
+
+    data = dict(status=rep['status_name'], gauge=rep['gauge'], anchor=rep['anchor'], sigma_px=float(sigma_px),
+                sigma_hat_px=lst(rep['sigma_hat_px']), dof=int(rep['dof']), min_pivot=lst(rep['min_pivot']),
+                parameters='per camera (dw, dt): R <- exp([dw]x) R (rad), t <- t + dt (m)',
+                cameras=[dict(cov=lst(blocks[c]), rotation_sd=lst(sd[c, :3]), translation_sd=lst(sd[c, 3:]),
+                              centre=lst(camera_centres(r_arr, t_arr)[c]),
+                              centre_cov=lst(camera_centre_covariance(blocks[c], r_arr[c], t_arr[c])))
+                         for c in range(len(blocks))])
+    with open(fpath, 'w') as f:
+        json.dump(data, f, indent=2)

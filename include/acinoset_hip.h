@@ -395,6 +395,70 @@ int acs_sba_extrinsics(acs_ctx* ctx, double* cams, int32_t n_cams, const double*
                        int64_t n_pts, const acs_sba_ext_opts* opts, double* resid_before,
                        double* resid_after, acs_sba_ext_report* report, uint32_t flags);
 
+/* ---- camera-pose and joint point covariances of the points + extrinsics SBA -----------
+ * Evaluated at the cameras (fisheye records, n_cams <= 16) and points passed in; nothing is
+ * solved. Observation list as acs_sba_extrinsics.
+ * Linearisation: the solver's own. Per camera (dw, dt) with R <- exp([dw]x) R, t <- t + dt, so
+ * J_cam = J_Y [-[R X]x | I], J_pt = J_Y R; Triggs weights wh = max((1 - z) w^2, 0.1 w),
+ * w = 1 / (1 + z), z = r^2 / f_scale^2.
+ * Points: status by the rule of acs_sba_points_covariance on the point's own V = sum wh J_pt^T
+ * J_pt (ACS_COV_NOOBS without a usable observation, ACS_COV_DEGENERATE when an LDL^T pivot fails
+ * d > 1e-9 max(V00, V11, V22), else ACS_COV_OK). A point that is not OK is left out entirely
+ * (its U, W and V terms): a single-view point carries no information about the cameras.
+ * Reduced system: S = sum U - sum_OK W V^-1 W^T (6C x 6C, undamped, symmetrised).
+ * Gauge generators G (6C x 7), per camera c: rotation theta: dw = -R_c theta, dt = 0;
+ * translation tau: dw = 0, dt = -R_c tau; scale: dw = 0, dt = t_c. S G = 0.
+ * ACS_GAUGE_FREE (inner constraints over the camera parameters, minimum trace): with Q an
+ * orthonormal basis of span G and mu = max diag S,
+ *   cov = sigma_px^2 [(S + mu Q Q^T)^-1 - Q Q^T / mu]   (= sigma_px^2 pinv(S)).
+ * ACS_GAUGE_ANCHOR: the pose of camera anchor_cam (a) and the distance between the centres of
+ * a and scale_cam (b) are held. Cm (7 x 6C) = six identity rows on camera a and the row
+ * e^T dc_b/d(dw_b, dt_b), c = -R^T t, dc/d(dw, dt) = [-R^T [t]x | -R^T], e the unit baseline;
+ *   cov = P cov_free P^T,  P = I - G (Cm G)^-1 Cm,
+ * camera a's rows and columns exact zeros.
+ * Degenerate problem: with Ah = S + mu Q Q^T scaled to unit diagonal, status is
+ * ACS_EXT_COV_DEGENERATE when a diagonal entry is not > 0, a pivot of the unpivoted LDL^T of Ah
+ * in natural order fails d > 1e-9 (a NaN fails), or G has rank < 7 (one camera, or all centres
+ * in one place). Then every covariance is NaN. min_pivot = the smallest pivot up to and
+ * including the first that fails.
+ * Points (OK, B_i the 6C x 3 stack of the point's W blocks):
+ *   cov_i = sigma_px^2 V_i^-1 + V_i^-1 B_i^T cov_cc B_i V_i^-1,  NaN for the others.
+ * sigma_hat_px^2 = sum w r^2 / dof, dof = m - 3 n_ok - (6C - 7) over the residuals of the OK
+ * points (NaN when dof <= 0): reported, never applied.
+ * cov_cams (6C, 6C) with camera c's (dw, dt) at rows 6c..6c+5 (rad, m); cov_pts (n_pts, 3, 3)
+ * and pt_status (n_pts, int32) may be NULL; every matrix is exactly symmetric. The call waits
+ * for the stream. Invalid arguments (f_scale or sigma_px <= 0, n_cams outside 1..16, for the
+ * anchor gauge with n_cams >= 2: anchor_cam == scale_cam, either out of range, or coincident
+ * centres; ACS_CAMS_STANDARD) return ACS_E_INVALID before anything is staged.             */
+#define ACS_GAUGE_FREE 0
+#define ACS_GAUGE_ANCHOR 1
+#define ACS_EXT_COV_OK 0
+#define ACS_EXT_COV_DEGENERATE 1
+typedef struct {
+  int32_t gauge;       /* ACS_GAUGE_*; default ACS_GAUGE_ANCHOR */
+  int32_t anchor_cam;  /* default 0 */
+  int32_t scale_cam;   /* default 1 */
+  int32_t reserved;
+  double f_scale;      /* the solve's Cauchy scale; default 1 (acs_sba_ext_default_opts) */
+  double sigma_px;     /* assumed pixel noise; default 1 */
+} acs_sba_ext_cov_opts;
+typedef struct {
+  int32_t status;      /* ACS_EXT_COV_* */
+  int32_t reserved;
+  int64_t n_points, n_ok, n_noobs, n_degenerate;
+  int64_t dof;
+  double min_pivot;
+  double sigma_hat_px;
+  double rot_sd_max;    /* largest rotation sd over the cameras (rad) */
+  double trans_sd_max;  /* largest translation sd over the cameras (m) */
+} acs_sba_ext_cov_report;
+void acs_sba_ext_cov_default_opts(acs_sba_ext_cov_opts* o);
+int acs_sba_extrinsics_covariance(acs_ctx* ctx, const double* cams, int32_t n_cams, const double* uv,
+                                  const int32_t* pt_idx, const int32_t* cam_idx, int64_t n_obs,
+                                  const double* pts, int64_t n_pts, const acs_sba_ext_cov_opts* opts,
+                                  double* cov_cams, double* cov_pts, int32_t* pt_status,
+                                  acs_sba_ext_cov_report* report, uint32_t flags);
+
 /* ---- §8(e): points + extrinsics SBA over ranks -------------------------------------
  * Each rank passes its own points and their observations (point indices local to the
  * rank); cameras are replicated. ONE all-reduce per LM step:
