@@ -109,10 +109,47 @@ void* acs_out_buf(acs_ctx* ctx, int slot, void* dst, size_t bytes, uint32_t flag
 
 static inline int acs_grid(int64_t n, int block) { return (int)((n + block - 1) / block); }
 
-// Observation list (any order) -> per-point slot tensor (n_pts, K): uv_pad, mask, camid,
-// deterministic (stable radix sort by point id). Defined in sba.hip. *K_out = max obs/pt.
-int acs_obs_to_slots(acs_ctx* ctx, const double* duv, const int32_t* dpi, const int32_t* dci, int64_t n_obs,
-                     int64_t n_pts, int n_cams, double2** uv_pad, uint8_t** mask, uint8_t** camid, int* K_out);
+// An observation list (any order) on the device and its per-point slot tensor (n_pts, K): uvp, mask,
+// camid, deterministic (stable radix sort by point id); K = max obs/pt.
+struct ObsSlots {
+  const double *cams = nullptr, *uv = nullptr;
+  const int32_t *pt_idx = nullptr, *cam_idx = nullptr;
+  double* pts = nullptr;
+  double2* uvp = nullptr;
+  uint8_t *mask = nullptr, *camid = nullptr;
+  int K = 1;
+};
+// Stages (cams, uv, pt_idx, cam_idx, pts) and builds the slots (sba.hip). fn names the entry point
+// in the messages; a point with more than max_K observations is refused. Without observations:
+// one empty slot per point.
+int acs_stage_obs(acs_ctx* ctx, const char* fn, int max_K, int cam_stride, const double* cams, int n_cams,
+                  const double* uv, const int32_t* pt_idx, const int32_t* cam_idx, int64_t n_obs, const double* pts,
+                  int64_t n_pts, uint32_t flags, ObsSlots* o);
+
+// One point = one aligned group of G lanes, G = 2 .. 64: CALL(g) with the literal group size
+#define ACS_G_SWITCH(G, CALL) \
+  switch (G) {                \
+    case 2: CALL(2); break;   \
+    case 4: CALL(4); break;   \
+    case 8: CALL(8); break;   \
+    case 16: CALL(16); break; \
+    case 32: CALL(32); break; \
+    default: CALL(64); break; \
+  }
+
+// 256-byte aligned runs of doubles carved out of one allocation. With a null base only the size
+// is counted: a layout function runs once for bytes() and once more with the allocation.
+struct Arena {
+  double* base;
+  size_t off = 0;
+  template <class T = double>
+  T* take(size_t n_doubles) {
+    const size_t o = off;
+    off += ((n_doubles * sizeof(double) + 255) / 256) * 256 / sizeof(double);
+    return base ? (T*)(base + o) : nullptr;
+  }
+  size_t bytes() const { return off * sizeof(double); }
+};
 
 // ---- device-buffer stages shared by the entry points and the fused pipeline -------------
 // Dense points-only SBA (sba.hip): the fused LM over (n_pts, C) observation slots; with a
@@ -437,6 +474,36 @@ __device__ __forceinline__ double group_sum(double v) {
   if (G >= 32) v += __shfl_xor(v, 16, G);
   if (G >= 64) v += __shfl_xor(v, 32, G);
   return v;
+}
+
+// The point rule of both covariances (k_sba_cov, k_extcov_linearize). v: the point's 3x3
+// Gauss-Newton matrix, packed upper [00 01 02 11 12 22]. LDL^T without pivoting: H = L D L^T,
+// H^-1 = sum_k (1 / d_k) m_k^T m_k with m_k the rows of L^-1 = [1 0 0; -l10 1 0; l10 l21 - l20,
+// -l21, 1], into c (packed likewise). True when every pivot passes d > 1e-9 max(H00, H11, H22),
+// written so that a NaN pivot or threshold fails. rcp is the caller's reciprocal.
+#define ACS_COV_PIVOT_TOL 1e-9
+template <class Rcp>
+__device__ __forceinline__ bool ldl3_inverse(const double* v, Rcp rcp, double c[6]) {
+  const double d0 = v[0], i0 = rcp(d0);
+  const double l10 = v[1] * i0, l20 = v[2] * i0;
+  const double d1 = v[3] - l10 * v[1], i1 = rcp(d1);
+  const double t = v[4] - l20 * v[1];
+  const double l21 = t * i1;
+  const double d2 = v[5] - l20 * v[2] - l21 * t, i2 = rcp(d2);
+  const double thr = ACS_COV_PIVOT_TOL * fmax(v[0], fmax(v[3], v[5]));
+  const bool ok = d0 > thr && d1 > thr && d2 > thr;
+  const double m20 = l10 * l21 - l20;
+  c[5] = i2;
+  c[4] = -l21 * i2;
+  c[2] = m20 * i2;
+  c[3] = i1 + l21 * l21 * i2;
+  c[1] = -l10 * i1 - l21 * c[2];
+  c[0] = i0 + l10 * l10 * i1 + m20 * c[2];
+  return ok;
+}
+// ACS_COV_* of a point from its number of scalar residuals and ldl3_inverse's verdict
+__device__ __forceinline__ int cov_point_status(double n_res, bool pivots_ok) {
+  return n_res == 0.0 ? ACS_COV_NOOBS : pivots_ok ? ACS_COV_OK : ACS_COV_DEGENERATE;
 }
 
 // Row-broadcast group sums of k_sba_lm's ROW instances (sba.hip; one point per 16-lane DPP row, slots in lanes 0..K-1, K <= 8): the sums behind

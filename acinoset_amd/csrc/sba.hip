@@ -731,8 +731,9 @@ int acs_sba_dense_enqueue(acs_ctx* ctx, const double* dcams, int C, const double
   return ACS_OK;
 }
 
-int acs_obs_to_slots(acs_ctx* ctx, const double* duv, const int32_t* dpi, const int32_t* dci, int64_t n_obs,
-                     int64_t n_pts, int n_cams, double2** uv_pad, uint8_t** mask, uint8_t** camid, int* K_out) {
+// Observation list -> slot tensor (ObsSlots, common.hpp); the messages name the entry point fn
+static int obs_to_slots(acs_ctx* ctx, const char* fn, int max_K, int64_t n_obs, int64_t n_pts, int n_cams,
+                        ObsSlots* o) {
   hipStream_t s = ctx->stream;
   // stable sort of observation ids by point id
   int32_t* skey = (int32_t*)acs_ws(ctx, WS_SORT0, sizeof(int32_t) * n_obs);
@@ -743,40 +744,56 @@ int acs_obs_to_slots(acs_ctx* ctx, const double* duv, const int32_t* dpi, const 
   if (!skey || !vin || !sval || !cnt || !start) return ACS_E_NOMEM;
   hipLaunchKernelGGL(k_iota, dim3(acs_grid(n_obs, 256)), dim3(256), 0, s, vin, n_obs);
   size_t tb0 = 0, tb1 = 0, tb2 = 0;
-  ACS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, tb0, dpi, skey, (const int32_t*)vin, sval,
+  ACS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, tb0, o->pt_idx, skey, (const int32_t*)vin, sval,
                                                    (int)n_obs, 0, 32, s));
   ACS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, tb1, cnt, start, (int)n_pts, s));
   ACS_HIP(ctx, hipcub::DeviceReduce::Max(nullptr, tb2, cnt, cnt + n_pts, (int)n_pts, s));
   size_t tb = std::max(tb0, std::max(tb1, tb2));
   void* tmp = acs_ws(ctx, WS_SORT3, tb);
   if (!tmp) return ACS_E_NOMEM;
-  ACS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(tmp, tb, dpi, skey, (const int32_t*)vin, sval,
+  ACS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(tmp, tb, o->pt_idx, skey, (const int32_t*)vin, sval,
                                                    (int)n_obs, 0, 32, s));
   ACS_HIP(ctx, hipMemsetAsync(cnt, 0, sizeof(int32_t) * (n_pts + 2), s));
-  hipLaunchKernelGGL(k_count, dim3(acs_grid(n_obs, 256)), dim3(256), 0, s, dpi, n_obs, cnt, n_pts,
+  hipLaunchKernelGGL(k_count, dim3(acs_grid(n_obs, 256)), dim3(256), 0, s, o->pt_idx, n_obs, cnt, n_pts,
                      cnt + n_pts + 1);
   ACS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(tmp, tb, cnt, start, (int)n_pts, s));
   ACS_HIP(ctx, hipcub::DeviceReduce::Max(tmp, tb, cnt, cnt + n_pts, (int)n_pts, s));
   int32_t hk[2] = {0, 0};
   ACS_HIP(ctx, hipMemcpyAsync(hk, cnt + n_pts, sizeof(int32_t) * 2, hipMemcpyDeviceToHost, s));
   ACS_HIP(ctx, hipStreamSynchronize(s));
-  ACS_CHECK(ctx, hk[1] == 0, "acs_sba_points: %d point indices out of [0, %lld)", hk[1], (long long)n_pts);
+  ACS_CHECK(ctx, hk[1] == 0, "%s: %d point indices out of [0, %lld)", fn, hk[1], (long long)n_pts);
   const int K = hk[0] < 1 ? 1 : hk[0];
-  ACS_CHECK(ctx, K <= 256, "acs_sba_points: a point has %d observations (max 256)", K);
-  double2* uvp = (double2*)acs_ws(ctx, WS_TMP2, sizeof(double2) * n_pts * K);
-  uint8_t* mk = (uint8_t*)acs_ws(ctx, WS_TMP3, (size_t)n_pts * K);
-  uint8_t* cid = (uint8_t*)acs_ws(ctx, WS_TMP4, (size_t)n_pts * K);
-  if (!uvp || !mk || !cid) return ACS_E_NOMEM;
-  ACS_HIP(ctx, hipMemsetAsync(mk, 0, (size_t)n_pts * K, s));
+  ACS_CHECK(ctx, K <= max_K, "%s: a point has %d observations (max %d)", fn, K, max_K);
+  o->uvp = (double2*)acs_ws(ctx, WS_TMP2, sizeof(double2) * n_pts * K);
+  o->mask = (uint8_t*)acs_ws(ctx, WS_TMP3, (size_t)n_pts * K);
+  o->camid = (uint8_t*)acs_ws(ctx, WS_TMP4, (size_t)n_pts * K);
+  if (!o->uvp || !o->mask || !o->camid) return ACS_E_NOMEM;
+  ACS_HIP(ctx, hipMemsetAsync(o->mask, 0, (size_t)n_pts * K, s));
   hipLaunchKernelGGL(k_scatter_slots, dim3(acs_grid(n_obs, 256)), dim3(256), 0, s, skey, sval, n_obs, start,
-                     (const double2*)duv, dci, K, n_cams, uvp, mk, cid);
+                     (const double2*)o->uv, o->cam_idx, K, n_cams, o->uvp, o->mask, o->camid);
   ACS_HIP(ctx, hipGetLastError());
-
-  *uv_pad = uvp;
-  *mask = mk;
-  *camid = cid;
-  *K_out = K;
+  o->K = K;
   return ACS_OK;
+}
+
+int acs_stage_obs(acs_ctx* ctx, const char* fn, int max_K, int cam_stride, const double* cams, int n_cams,
+                  const double* uv, const int32_t* pt_idx, const int32_t* cam_idx, int64_t n_obs, const double* pts,
+                  int64_t n_pts, uint32_t flags, ObsSlots* o) {
+  int rc;
+  if ((rc = acs_stage_in(ctx, WS_CAMS, cams, sizeof(double) * cam_stride * n_cams, flags, (void**)&o->cams))) return rc;
+  if ((rc = acs_stage_in(ctx, WS_PTS, pts, sizeof(double) * 3 * n_pts, flags, (void**)&o->pts))) return rc;
+  if (n_obs == 0) {
+    o->uvp = (double2*)acs_ws(ctx, WS_TMP2, sizeof(double2) * n_pts);
+    o->mask = (uint8_t*)acs_ws(ctx, WS_TMP3, (size_t)n_pts);
+    o->camid = (uint8_t*)acs_ws(ctx, WS_TMP4, (size_t)n_pts);
+    if (!o->uvp || !o->mask || !o->camid) return ACS_E_NOMEM;
+    ACS_HIP(ctx, hipMemsetAsync(o->mask, 0, (size_t)n_pts, ctx->stream));
+    return ACS_OK;
+  }
+  if ((rc = acs_stage_in(ctx, WS_UV, uv, sizeof(double) * 2 * n_obs, flags, (void**)&o->uv))) return rc;
+  if ((rc = acs_stage_in(ctx, WS_PTIDX, pt_idx, sizeof(int32_t) * n_obs, flags, (void**)&o->pt_idx))) return rc;
+  if ((rc = acs_stage_in(ctx, WS_CAMIDX, cam_idx, sizeof(int32_t) * n_obs, flags, (void**)&o->cam_idx))) return rc;
+  return obs_to_slots(ctx, fn, max_K, n_obs, n_pts, n_cams, o);
 }
 
 extern "C" {
@@ -852,15 +869,13 @@ int acs_sba_points(acs_ctx* ctx, const double* cams, int32_t n_cams, const doubl
     if (report) std::memset(report, 0, sizeof(*report));
     return ACS_OK;
   }
-  void *dc, *duv, *dpi, *dci, *dp;
   int rc;
   const int model = acs_flags_model(flags);
   const auto k_res = model == ACS_MODEL_STANDARD ? k_residuals_ext<ACS_MODEL_STANDARD> : k_residuals_ext<ACS_MODEL_FISHEYE>;
-  if ((rc = acs_stage_in(ctx, WS_CAMS, cams, sizeof(double) * acs_cam_stride(model) * n_cams, flags, &dc))) return rc;
-  if ((rc = acs_stage_in(ctx, WS_UV, uv, sizeof(double) * 2 * n_obs, flags, &duv))) return rc;
-  if ((rc = acs_stage_in(ctx, WS_PTIDX, pt_idx, sizeof(int32_t) * n_obs, flags, &dpi))) return rc;
-  if ((rc = acs_stage_in(ctx, WS_CAMIDX, cam_idx, sizeof(int32_t) * n_obs, flags, &dci))) return rc;
-  if ((rc = acs_stage_in(ctx, WS_PTS, pts, sizeof(double) * 3 * n_pts, flags, &dp))) return rc;
+  ObsSlots o;
+  if ((rc = acs_stage_obs(ctx, "acs_sba_points", 256, acs_cam_stride(model), cams, n_cams, uv, pt_idx, cam_idx, n_obs,
+                          pts, n_pts, flags, &o)))
+    return rc;
   hipStream_t s = ctx->stream;
 
   // residuals at the initial points (residuals['before'])
@@ -868,35 +883,26 @@ int acs_sba_points(acs_ctx* ctx, const double* cams, int32_t n_cams, const doubl
   if (resid_before) {
     drb = (double*)acs_out_buf(ctx, WS_OUT0, resid_before, sizeof(double) * 2 * n_obs, flags);
     if (!drb) return ACS_E_NOMEM;
-    hipLaunchKernelGGL(k_res, dim3(acs_grid(n_obs, 256)), dim3(256), 0, s, (const double*)dc, n_cams,
-                       (const double*)duv, (const int32_t*)dpi, (const int32_t*)dci, n_obs, (const double*)dp, n_pts,
-                       drb);
+    hipLaunchKernelGGL(k_res, dim3(acs_grid(n_obs, 256)), dim3(256), 0, s, o.cams, n_cams, o.uv, o.pt_idx, o.cam_idx,
+                       n_obs, (const double*)o.pts, n_pts, drb);
     ACS_HIP(ctx, hipGetLastError());
   }
 
-  double2* uvp;
-  uint8_t *mk, *cid;
-  int K;
-  if ((rc = acs_obs_to_slots(ctx, (const double*)duv, (const int32_t*)dpi, (const int32_t*)dci, n_obs, n_pts, n_cams,
-                             &uvp, &mk, &cid, &K)))
-    return rc;
-
   double *c0, *c1;
   int* st;
-  if ((rc = run_lm(ctx, model, (const double*)dc, n_cams, K, uvp, mk, cid, n_pts, (const double*)dp, (double*)dp, opts,
-                   report != nullptr, &c0, &c1, &st)))
+  if ((rc = run_lm(ctx, model, o.cams, n_cams, o.K, o.uvp, o.mask, o.camid, n_pts, o.pts, o.pts, opts, report != nullptr,
+                   &c0, &c1, &st)))
     return rc;
 
   double* dra = nullptr;
   if (resid_after) {
     dra = (double*)acs_out_buf(ctx, WS_OUT1, resid_after, sizeof(double) * 2 * n_obs, flags);
     if (!dra) return ACS_E_NOMEM;
-    hipLaunchKernelGGL(k_res, dim3(acs_grid(n_obs, 256)), dim3(256), 0, s, (const double*)dc, n_cams,
-                       (const double*)duv, (const int32_t*)dpi, (const int32_t*)dci, n_obs, (const double*)dp, n_pts,
-                       dra);
+    hipLaunchKernelGGL(k_res, dim3(acs_grid(n_obs, 256)), dim3(256), 0, s, o.cams, n_cams, o.uv, o.pt_idx, o.cam_idx,
+                       n_obs, (const double*)o.pts, n_pts, dra);
     ACS_HIP(ctx, hipGetLastError());
   }
-  if ((rc = acs_stage_out(ctx, pts, dp, sizeof(double) * 3 * n_pts, flags))) return rc;
+  if ((rc = acs_stage_out(ctx, pts, o.pts, sizeof(double) * 3 * n_pts, flags))) return rc;
   if (resid_before && (rc = acs_stage_out(ctx, resid_before, drb, sizeof(double) * 2 * n_obs, flags))) return rc;
   if (resid_after && (rc = acs_stage_out(ctx, resid_after, dra, sizeof(double) * 2 * n_obs, flags))) return rc;
   if (report) {

@@ -4,9 +4,9 @@
 // r_od in pixels at the points passed in, z = r^2 / f_scale^2 and w = 1 / (1 + z),
 //   H_i = sum_o sum_d wh_od J_od^T J_od,  wh = max((1 - z) w^2, 0.1 w)
 // is the Triggs-weighted Gauss-Newton matrix k_sba_lm (sba.hip) factorises on every pass, here
-// undamped; cov_i = sigma_px^2 H_i^-1 by an LDL^T without pivoting. The point is degenerate
-// when a pivot fails d > 1e-9 max(H00, H11, H22), written so that a NaN fails it. Nothing is
-// solved: one evaluation and one 3x3 inverse per point.
+// undamped; cov_i = sigma_px^2 H_i^-1. The inverse, the pivot rule that makes a point degenerate
+// and the status are ldl3_inverse and cov_point_status (common.hpp), shared with the extrinsics
+// covariance. Nothing is solved: one evaluation and one 3x3 inverse per point.
 //
 // Mapping: one point = one aligned group of G = clamp(nextpow2(K), 2, 64) lanes over the
 // (n_pts, K) slot tensor of k_sba_lm, slots strided over the lanes (slot = lane, lane + G, ...),
@@ -68,27 +68,14 @@ __global__ __launch_bounds__(256) void k_sba_cov(const double2* __restrict__ uv,
 #pragma unroll
   for (int i = 0; i < 8; ++i) v[i] = group_sum<G>(v[i]);
   if (lane != 0) return;  // the inverse and the record are lane 0's alone
-  // LDL^T without pivoting: H = L D L^T, H^-1 = sum_k (1 / d_k) m_k^T m_k with m_k the rows of
-  // L^-1 = [1 0 0; -l10 1 0; l10 l21 - l20, -l21, 1]
-  const double d0 = v[0], i0 = rcp_nr(d0);
-  const double l10 = v[1] * i0, l20 = v[2] * i0;
-  const double d1 = v[3] - l10 * v[1], i1 = rcp_nr(d1);
-  const double t = v[4] - l20 * v[1];
-  const double l21 = t * i1;
-  const double d2 = v[5] - l20 * v[2] - l21 * t, i2 = rcp_nr(d2);
-  const double thr = 1e-9 * fmax(v[0], fmax(v[3], v[5]));
-  const bool ok = d0 > thr && d1 > thr && d2 > thr;  // a NaN pivot or threshold fails
-  const int st = v[7] == 0.0 ? ACS_COV_NOOBS : ok ? ACS_COV_OK : ACS_COV_DEGENERATE;
-  const double m20 = l10 * l21 - l20;
-  const double c22 = i2, c12 = -l21 * i2, c02 = m20 * i2;
-  const double c11 = i1 + l21 * l21 * i2;
-  const double c01 = -l10 * i1 - l21 * c02;
-  const double c00 = i0 + l10 * l10 * i1 + m20 * c02;
+  double ci[6];
+  const bool ok = ldl3_inverse(v, [](double d) { return rcp_nr(d); }, ci);
+  const int st = cov_point_status(v[7], ok);
   const double nan = __builtin_nan("");
   const bool good = st == ACS_COV_OK;
   double* c = cov + 9 * p;
-  const double e00 = good ? s2 * c00 : nan, e01 = good ? s2 * c01 : nan, e02 = good ? s2 * c02 : nan;
-  const double e11 = good ? s2 * c11 : nan, e12 = good ? s2 * c12 : nan, e22 = good ? s2 * c22 : nan;
+  const double e00 = good ? s2 * ci[0] : nan, e01 = good ? s2 * ci[1] : nan, e02 = good ? s2 * ci[2] : nan;
+  const double e11 = good ? s2 * ci[3] : nan, e12 = good ? s2 * ci[4] : nan, e22 = good ? s2 * ci[5] : nan;
   c[0] = e00;
   c[1] = e01;
   c[2] = e02;
@@ -158,22 +145,15 @@ __global__ __launch_bounds__(256) void k_sba_cov_report(const double* __restrict
 }
 
 template <bool CAMID, int MODEL>
-static int launch_cov_g(acs_ctx* ctx, int G, int blocks, int block, const double2* uv, const uint8_t* mask,
-                        int64_t n_pts, const double* pts, const double* cams, int K, int C, const uint8_t* camid,
-                        double if2, double s2, double* cov, int32_t* status, double* wr2, int32_t* nres) {
+static void launch_cov_g(acs_ctx* ctx, int G, int blocks, int block, const double2* uv, const uint8_t* mask,
+                         int64_t n_pts, const double* pts, const double* cams, int K, int C, const uint8_t* camid,
+                         double if2, double s2, double* cov, int32_t* status, double* wr2, int32_t* nres) {
   const size_t lds = sizeof(double) * CamRec<MODEL>::stride * C;
-  switch (G) {
-#define ACS_G(g)                                                                                                  \
-  case g:                                                                                                         \
-    hipLaunchKernelGGL((k_sba_cov<g, CAMID, MODEL>), dim3(blocks), dim3(block), lds, ctx->stream, uv, mask, n_pts, \
-                       pts, cams, K, C, camid, if2, s2, cov, status, wr2, nres);                                  \
-    break;
-    ACS_G(2) ACS_G(4) ACS_G(8) ACS_G(16) ACS_G(32) ACS_G(64)
-#undef ACS_G
-    default:
-      return acs_fail(ctx, ACS_E_INVALID, "unsupported group size %d", G);
-  }
-  return ACS_OK;
+#define COV_G(g)                                                                                                 \
+  hipLaunchKernelGGL((k_sba_cov<g, CAMID, MODEL>), dim3(blocks), dim3(block), lds, ctx->stream, uv, mask, n_pts, \
+                     pts, cams, K, C, camid, if2, s2, cov, status, wr2, nres)
+  ACS_G_SWITCH(G, COV_G)
+#undef COV_G
 }
 
 // The covariance kernel (and, with a report, its reduction) over an (n_pts, K) slot tensor
@@ -201,13 +181,11 @@ static int run_cov(acs_ctx* ctx, int model, const double* dcams, int C, int K, c
   const int blocks = acs_grid(threads, block);
   const double if2 = 1.0 / (f_scale * f_scale), s2 = sigma_px * sigma_px;
 #define ACS_COV_ARGS ctx, G, blocks, block, duv, dmask, n_pts, dpts, dcams, K, C, dcamid, if2, s2, dcov, dstatus, wr2, nres
-  int rc;
   if (model == ACS_MODEL_STANDARD)
-    rc = dcamid ? launch_cov_g<true, ACS_MODEL_STANDARD>(ACS_COV_ARGS) : launch_cov_g<false, ACS_MODEL_STANDARD>(ACS_COV_ARGS);
+    dcamid ? launch_cov_g<true, ACS_MODEL_STANDARD>(ACS_COV_ARGS) : launch_cov_g<false, ACS_MODEL_STANDARD>(ACS_COV_ARGS);
   else
-    rc = dcamid ? launch_cov_g<true, ACS_MODEL_FISHEYE>(ACS_COV_ARGS) : launch_cov_g<false, ACS_MODEL_FISHEYE>(ACS_COV_ARGS);
+    dcamid ? launch_cov_g<true, ACS_MODEL_FISHEYE>(ACS_COV_ARGS) : launch_cov_g<false, ACS_MODEL_FISHEYE>(ACS_COV_ARGS);
 #undef ACS_COV_ARGS
-  if (rc) return rc;
   ACS_HIP(ctx, hipGetLastError());
   if (report) {
     hipLaunchKernelGGL(k_sba_cov_report, dim3(1), dim3(256), 0, ctx->stream, (const double*)dcov,
@@ -272,37 +250,17 @@ int acs_sba_points_covariance(acs_ctx* ctx, const double* cams, int32_t n_cams, 
     if (report) std::memset(report, 0, sizeof(*report));
     return ACS_OK;
   }
-  void *dc, *duv = nullptr, *dpi = nullptr, *dci = nullptr, *dp;
   int rc;
   const int model = acs_flags_model(flags);
-  if ((rc = acs_stage_in(ctx, WS_CAMS, cams, sizeof(double) * acs_cam_stride(model) * n_cams, flags, &dc))) return rc;
-  if ((rc = acs_stage_in(ctx, WS_PTS, pts, sizeof(double) * 3 * n_pts, flags, &dp))) return rc;
+  ObsSlots o;  // without observations every point is ACS_COV_NOOBS
+  if ((rc = acs_stage_obs(ctx, "acs_sba_points_covariance", 256, acs_cam_stride(model), cams, n_cams, uv, pt_idx,
+                          cam_idx, n_obs, pts, n_pts, flags, &o)))
+    return rc;
   double* dcov = (double*)acs_out_buf(ctx, WS_OUT0, cov, sizeof(double) * 9 * n_pts, flags);
   int32_t* dst = status ? (int32_t*)acs_out_buf(ctx, WS_OUT1, status, sizeof(int32_t) * n_pts, flags) : nullptr;
   if (!dcov || (status && !dst)) return ACS_E_NOMEM;
-  double2* uvp;
-  uint8_t *mk, *cid;
-  int K = 1;
-  if (n_obs > 0) {
-    if ((rc = acs_stage_in(ctx, WS_UV, uv, sizeof(double) * 2 * n_obs, flags, &duv))) return rc;
-    if ((rc = acs_stage_in(ctx, WS_PTIDX, pt_idx, sizeof(int32_t) * n_obs, flags, &dpi))) return rc;
-    if ((rc = acs_stage_in(ctx, WS_CAMIDX, cam_idx, sizeof(int32_t) * n_obs, flags, &dci))) return rc;
-    if ((rc = acs_obs_to_slots(ctx, (const double*)duv, (const int32_t*)dpi, (const int32_t*)dci, n_obs, n_pts, n_cams,
-                               &uvp, &mk, &cid, &K))) {
-      // the shared slot builder words its errors for acs_sba_points: name this entry point
-      ctx->err = "acs_sba_points_covariance: " + ctx->err;
-      return rc;
-    }
-  } else {
-    // no observation at all: one empty slot per point, every point ACS_COV_NOOBS
-    uvp = (double2*)acs_ws(ctx, WS_TMP2, sizeof(double2) * n_pts);
-    mk = (uint8_t*)acs_ws(ctx, WS_TMP3, (size_t)n_pts);
-    cid = (uint8_t*)acs_ws(ctx, WS_TMP4, (size_t)n_pts);
-    if (!uvp || !mk || !cid) return ACS_E_NOMEM;
-    ACS_HIP(ctx, hipMemsetAsync(mk, 0, (size_t)n_pts, ctx->stream));
-  }
-  if ((rc = run_cov(ctx, model, (const double*)dc, n_cams, K, uvp, mk, cid, n_pts, (const double*)dp, f_scale, sigma_px,
-                    dcov, dst, report)))
+  if ((rc = run_cov(ctx, model, o.cams, n_cams, o.K, o.uvp, o.mask, o.camid, n_pts, o.pts, f_scale, sigma_px, dcov, dst,
+                    report)))
     return rc;
   return finish_cov(ctx, n_pts, cov, dcov, status, dst, report != nullptr, flags);
 }

@@ -6,12 +6,13 @@
 // (create_bundle_adjustment_jacobian_sparsity_matrix :11-22 with 6 camera columns).
 //
 // LM with the points eliminated by Schur complement (spec: oracle/sba_ext.py):
-//   k_ext_linearize [point groups] per observation: residual, J_pt = J_Y R, J_cam =
-//                   J_Y [-[R X]x | I]; per point V (3x3), g_p; per slot the camera-side
-//                   blocks U (6x6), g_c (6), W = J_cam^T J_pt (6x3). One point = one
-//                   aligned lane group (as k_sba_lm), butterfly sums.
-//   k_ext_schur     [point chunks] fixed-order partial reduced camera system
-//                   S = U - sum W M W^T, b = -g_c + sum W M g_p, M = (V + lam D)^-1
+//   k_ext_linearize [point groups] per observation (ext_obs_blocks, sba_ext.hpp): residual,
+//                   J_pt = J_Y R, J_cam = J_Y [-[R X]x | I] and the slot record's U (6x6), W =
+//                   J_cam^T J_pt (6x3); here g_c (6) behind them and per point V (3x3), g_p. One
+//                   point = one aligned lane group (ACS_G_SWITCH), butterfly sums (group_sum).
+//   k_ext_schur     [point chunks] fixed-order partial reduced camera system (ext_schur_stage,
+//                   ext_schur_entry with M = (V + lam D)^-1) S = U - sum W M W^T, and here
+//                   b = -g_c + sum W M g_p, diag U, g_c
 //   k_ext_solve     [1 block] chunk sums in order, Marquardt damping, SPD inverse
 //                   (blocked Gauss-Jordan on f64 MFMA tiles), camera step
 //   k_ext_back      [points] point steps dX = -M (g_p + sum W^T dc), trial points
@@ -24,16 +25,10 @@
 #include "mfma64.hpp"
 #include "sba_ext.hpp"
 
-#define EXT_Q 45  // per slot: U (21 packed upper) + g_c (6) + W (18)
 // damping floor: the 7-DoF similarity gauge is left free (as in the reference), so the
 // reduced camera system is singular up to lambda; below ~1e-8 its gauge directions are
 // resolved by rounding alone. Spec shared with oracle/sba_ext.py (LAM_MIN).
 #define EXT_LAM_MIN 1e-7
-
-struct ExtDims {
-  int n, K, C, G, chunk;  // chunk: points per k_ext_schur block (LDS-sized)
-  double f2;
-};
 
 struct ExtState {
   double F, F0, lam, gmax, dnorm, xnorm;
@@ -72,45 +67,25 @@ __global__ __launch_bounds__(256) void k_ext_linearize(ExtDims d, const ExtState
   double V[6] = {0, 0, 0, 0, 0, 0}, gp[3] = {0, 0, 0}, F = 0.0;
   for (int slot = lane; slot < d.K; slot += G) {
     const int64_t o = p * d.K + slot;
-    double* q = Q + (size_t)o * EXT_Q;
+    double* q = Q + (size_t)o * EXT_Q<true>;
     if (!mask[o] || camid[o] >= d.C) {
-      for (int e = 0; e < EXT_Q; ++e) q[e] = 0.0;
+      for (int e = 0; e < EXT_Q<true>; ++e) q[e] = 0.0;
       continue;
     }
-    const double* c = s_cam + camid[o] * ACS_CAM_STRIDE;
-    ProjOut po;
-    fisheye_project<true>(c, X0, X1, X2, po);
-    const double2 m = uv[o];
-    const double r[2] = {po.u - m.x, po.v - m.y};
-    // R X = Y - t
-    const double v0 = po.Y[0] - c[17], v1 = po.Y[1] - c[18], v2 = po.Y[2] - c[19];
-    double U[21];
-    for (int e = 0; e < 21; ++e) U[e] = 0.0;
-    double gc[6] = {0, 0, 0, 0, 0, 0}, W[18];
-    for (int e = 0; e < 18; ++e) W[e] = 0.0;
+    ExtObs ob;
+    ext_obs_blocks(s_cam + camid[o] * ACS_CAM_STRIDE, X0, X1, X2, uv[o], d.f2, ob, q);
+    double gc[6] = {0, 0, 0, 0, 0, 0};
     for (int dd = 0; dd < 2; ++dd) {
-      const double* jy = po.JY + 3 * dd;
-      const double* jp = po.J + 3 * dd;
-      // J_cam = [-(J_Y [v]x), J_Y]
-      const double jc[6] = {-(jy[1] * v2 - jy[2] * v1), -(jy[2] * v0 - jy[0] * v2), -(jy[0] * v1 - jy[1] * v0),
-                            jy[0], jy[1], jy[2]};
-      const double z = r[dd] * r[dd] / d.f2;
-      const double w = 1.0 / (1.0 + z);
-      const double wh = fmax((1.0 - z) * w * w, 0.1 * w);
-      F += 0.5 * d.f2 * log1p(z);
-      for (int i = 0; i < 6; ++i) {
-        gc[i] += w * r[dd] * jc[i];
-        for (int j = i; j < 6; ++j) U[upk(i, j)] += wh * jc[i] * jc[j];
-        for (int j = 0; j < 3; ++j) W[i * 3 + j] += wh * jc[i] * jp[j];
-      }
+      const double *jc = ob.jc[dd], *jp = ob.jp[dd];
+      const double w = ob.w[dd], wh = ob.wh[dd];
+      F += 0.5 * d.f2 * log1p(ob.z[dd]);
+      for (int i = 0; i < 6; ++i) gc[i] += w * ob.r[dd] * jc[i];
       for (int i = 0; i < 3; ++i) {
-        gp[i] += w * r[dd] * jp[i];
+        gp[i] += w * ob.r[dd] * jp[i];
         for (int j = i; j < 3; ++j) V[i == 0 ? j : (i == 1 ? 2 + j : 5)] += wh * jp[i] * jp[j];
       }
     }
-    for (int e = 0; e < 21; ++e) q[e] = U[e];
-    for (int e = 0; e < 6; ++e) q[21 + e] = gc[e];
-    for (int e = 0; e < 18; ++e) q[27 + e] = W[e];
+    for (int e = 0; e < 6; ++e) q[EXT_Q_GC + e] = gc[e];
   }
   for (int e = 0; e < 6; ++e) V[e] = group_sum<G>(V[e]);
   for (int e = 0; e < 3; ++e) gp[e] = group_sum<G>(gp[e]);
@@ -160,54 +135,29 @@ __global__ __launch_bounds__(256) void k_ext_schur(ExtDims d, const ExtState* __
   double* sZ = lds;                              // np x K x 18  (W M)
   double* sg = sZ + (size_t)d.chunk * d.K * 18;  // np x 3 (g_p)
   int* scam = (int*)(sg + d.chunk * 3);          // np x K camera id (-1 = none)
-  for (int t = threadIdx.x; t < np; t += blockDim.x) {
-    const int p = p0 + t;
-    double M[9];
+  ext_schur_stage<true>(d, p0, np, Q, mask, camid, sZ, scam, [&](int p, int t, double* M) {
     point_minv(Vg + (size_t)p * 10, lam, M);
     for (int j = 0; j < 3; ++j) sg[t * 3 + j] = Vg[(size_t)p * 10 + 6 + j];
-    for (int s = 0; s < d.K; ++s) {
-      const int64_t o = (int64_t)p * d.K + s;
-      const bool ok = mask[o] && camid[o] < d.C;
-      scam[t * d.K + s] = ok ? camid[o] : -1;
-      const double* W = Q + (size_t)o * EXT_Q + 27;
-      for (int i = 0; i < 6; ++i)
-        for (int j = 0; j < 3; ++j)
-          sZ[((size_t)t * d.K + s) * 18 + i * 3 + j] =
-              ok ? W[i * 3] * M[j] + W[i * 3 + 1] * M[3 + j] + W[i * 3 + 2] * M[6 + j] : 0.0;
-    }
-  }
-  __syncthreads();
+    return true;
+  });
   for (int e = threadIdx.x; e < nE; e += blockDim.x) {
     double acc = 0.0;
     if (e < NC * NC) {
-      const int a = e / NC, b = e % NC, c1 = a / 6, k1 = a % 6, c2 = b / 6, k2 = b % 6;
-      for (int t = 0; t < np; ++t) {
-        const int64_t base = (int64_t)(p0 + t) * d.K;
-        for (int s1 = 0; s1 < d.K; ++s1) {
-          if (scam[t * d.K + s1] != c1) continue;
-          if (c1 == c2) acc += Q[(size_t)(base + s1) * EXT_Q + upk(k1, k2)];
-          const double* z = sZ + ((size_t)t * d.K + s1) * 18 + k1 * 3;
-          for (int s2 = 0; s2 < d.K; ++s2) {
-            if (scam[t * d.K + s2] != c2) continue;
-            const double* w = Q + (size_t)(base + s2) * EXT_Q + 27 + k2 * 3;
-            acc -= z[0] * w[0] + z[1] * w[1] + z[2] * w[2];
-          }
-        }
-      }
+      acc = ext_schur_entry<true>(d, p0, np, Q, sZ, scam, e / NC, e % NC);
     } else {
       const int r = e - NC * NC, kind = r / NC, a = r % NC, c1 = a / 6, k1 = a % 6;
       for (int t = 0; t < np; ++t) {
         const int64_t base = (int64_t)(p0 + t) * d.K;
         for (int s1 = 0; s1 < d.K; ++s1) {
           if (scam[t * d.K + s1] != c1) continue;
-          const double* q = Q + (size_t)(base + s1) * EXT_Q;
+          const double* q = Q + (size_t)(base + s1) * EXT_Q<true>;
           if (kind == 0) {  // b = -g_c + Z g_p
             const double* z = sZ + ((size_t)t * d.K + s1) * 18 + k1 * 3;
-            acc += -q[21 + k1] + z[0] * sg[t * 3] + z[1] * sg[t * 3 + 1] + z[2] * sg[t * 3 + 2];
+            acc += -q[EXT_Q_GC + k1] + z[0] * sg[t * 3] + z[1] * sg[t * 3 + 1] + z[2] * sg[t * 3 + 2];
           } else if (kind == 1) {  // U diagonal
-            acc += q[upk(k1, k1)];
+            acc += q[EXT_Q_U + upk(k1, k1)];
           } else {  // g_c
-            acc += q[21 + k1];
+            acc += q[EXT_Q_GC + k1];
           }
         }
       }
@@ -313,7 +263,7 @@ __global__ __launch_bounds__(256) void k_ext_back(ExtDims d, const ExtState* __r
   for (int s = 0; s < d.K; ++s) {
     const int64_t o = p * d.K + s;
     if (!mask[o] || camid[o] >= d.C) continue;
-    const double* W = Q + (size_t)o * EXT_Q + 27;
+    const double* W = Q + (size_t)o * EXT_Q<true> + EXT_Q_W;
     const double* dcc = dc + 6 * camid[o];
     for (int j = 0; j < 3; ++j)
       for (int i = 0; i < 6; ++i) acc[j] += W[i * 3 + j] * dcc[i];
@@ -398,6 +348,42 @@ __global__ __launch_bounds__(256) void k_ext_cost(ExtDims d, const ExtState* __r
   if (lane == 0) Fp[p] = F;
 }
 
+// The LM decision on a trial, by one thread: cost f, the points' step and state norms^2 dn and xn
+// (the cameras' are added here); the stop tests, then accept (swap the state, relax the damping)
+// or reject (raise it).
+__device__ __forceinline__ void ext_lm_decide(const ExtDims& d, ExtState* st, const ExtOpts& o, double f, double dn,
+                                              double xn, const double* camnorm) {
+  for (int c = 0; c < d.C; ++c) {
+    dn += camnorm[2 * c];
+    xn += camnorm[2 * c + 1];
+  }
+  if (st->gmax <= o.gtol) {
+    st->status = ACS_STATUS_GTOL;
+    return;
+  }
+  st->iters += 1;
+  st->dnorm = sqrt(dn);
+  st->xnorm = sqrt(xn);
+  const bool small = sqrt(dn) <= o.xtol * (o.xtol + sqrt(xn));
+  if (f < st->F) {
+    const bool fconv = (st->F - f) <= o.ftol * fabs(st->F);
+    st->nacc += 1;
+    st->F = f;
+    st->cur ^= 1;
+    st->lam = fmax(st->lam * 0.1, EXT_LAM_MIN);
+    st->relin = 1;
+    if (fconv)
+      st->status = ACS_STATUS_FTOL;
+    else if (small)
+      st->status = ACS_STATUS_XTOL;
+  } else {
+    st->lam *= 10.0;
+    st->relin = 0;
+    if (st->lam > 1e16) st->status = ACS_STATUS_STALLED;
+  }
+  if (st->status == 0 && st->iters >= o.max_iters) st->status = ACS_STATUS_MAXITER;
+}
+
 __global__ __launch_bounds__(256) void k_ext_lm(ExtDims d, ExtState* __restrict__ st, ExtOpts o, int init,
                                                 const double* __restrict__ Fp, const double* __restrict__ normp,
                                                 const double* __restrict__ camnorm) {
@@ -430,60 +416,120 @@ __global__ __launch_bounds__(256) void k_ext_lm(ExtDims d, ExtState* __restrict_
   if (st->status != 0) return;
   dn = bsum(dn);
   xn = bsum(xn);
-  if (tid != 0) return;
-  for (int c = 0; c < d.C; ++c) {
-    dn += camnorm[2 * c];
-    xn += camnorm[2 * c + 1];
-  }
-  if (st->gmax <= o.gtol) {
-    st->status = ACS_STATUS_GTOL;
-    return;
-  }
-  st->iters += 1;
-  st->dnorm = sqrt(dn);
-  st->xnorm = sqrt(xn);
-  const bool small = sqrt(dn) <= o.xtol * (o.xtol + sqrt(xn));
-  if (f < st->F) {
-    const bool fconv = (st->F - f) <= o.ftol * fabs(st->F);
-    st->nacc += 1;
-    st->F = f;
-    st->cur ^= 1;
-    st->lam = fmax(st->lam * 0.1, EXT_LAM_MIN);
-    st->relin = 1;
-    if (fconv)
-      st->status = ACS_STATUS_FTOL;
-    else if (small)
-      st->status = ACS_STATUS_XTOL;
-  } else {
-    st->lam *= 10.0;
-    st->relin = 0;
-    if (st->lam > 1e16) st->status = ACS_STATUS_STALLED;
-  }
-  if (st->status == 0 && st->iters >= o.max_iters) st->status = ACS_STATUS_MAXITER;
+  if (tid == 0) ext_lm_decide(d, st, o, f, dn, xn, camnorm);
 }
 
 // ---------------------------------------------------------------------------------------
-static size_t ext_schur_lds(const ExtDims& d) {
-  return sizeof(double) * ((size_t)d.chunk * d.K * 18 + d.chunk * 3) + sizeof(int) * d.chunk * d.K;
+// The device buffers of one solve, one allocation laid out by ext_layout.
+struct ExtBuffers {
+  double *cams, *pts;  // the current and the trial state: [2][C] records, [2][n][3]
+  double *Q, *Vg, *Fp, *part, *dc, *Sg, *normp, *camnorm;
+  ExtState* st;
+  int* bad;
+  double2* uvp;  // the slot tensor: the workspace's, or (own_slots) a copy behind the rest
+  uint8_t *mk, *cid;
+  int nchunk;
+};
+
+// the buffers at base; with a null base only the size in bytes (Arena)
+static size_t ext_layout(ExtBuffers& b, double* base, const ExtDims& d, bool own_slots) {
+  const size_t n = d.n, NC = 6 * d.C, slots = n * d.K;
+  Arena a{base};
+  b.nchunk = ext_nchunk(d);
+  b.cams = a.take(2 * (size_t)d.C * ACS_CAM_STRIDE);
+  b.pts = a.take(6 * n);
+  b.Q = a.take(slots * EXT_Q<true>);
+  b.Vg = a.take(n * 10);
+  b.Fp = a.take(n);
+  b.part = a.take(b.nchunk * (NC * NC + 3 * NC));
+  b.dc = a.take(96);
+  b.Sg = a.take(96 * 96);
+  b.normp = a.take(2 * n);
+  b.camnorm = a.take(64);
+  b.st = a.take<ExtState>(16);
+  b.bad = a.take<int>(2);
+  if (own_slots) {
+    b.uvp = a.take<double2>(2 * slots);
+    b.mk = a.take<uint8_t>((slots + 7) / 8);
+    b.cid = a.take<uint8_t>((slots + 7) / 8);
+  }
+  return a.bytes();
 }
 
-template <int G>
-static void ext_enqueue(hipStream_t s, const ExtDims& d, ExtState* st, const ExtOpts& o, double* cams, double* pts,
-                        const double2* uv, const uint8_t* mk, const uint8_t* cid, double* Q, double* Vg, double* Fp,
-                        double* part, double* dc, double* Sg, double* normp, double* camnorm, int* bad,
-                        int nchunk) {
-  const int blocks = acs_grid((int64_t)d.n * G, 256);
-  const size_t lds = ext_schur_lds(d);
-  const int NP = ((6 * d.C + 15) / 16) * 16;
-  const size_t lds_solve = sizeof(double) * ((size_t)NP * (NP + 1) + NP + 512 + 256);
-  hipLaunchKernelGGL((k_ext_linearize<G>), dim3(blocks), dim3(256), 0, s, d, st, cams, pts, uv, mk, cid, Q, Vg, Fp);
-  hipLaunchKernelGGL(k_ext_schur, dim3(nchunk), dim3(256), lds, s, d, st, Q, Vg, mk, cid, part);
-  hipLaunchKernelGGL(k_ext_solve, dim3(1), dim3(256), lds_solve, s, d, st, nchunk, part, Vg, d.n, nullptr, 0, dc, Sg,
-                     bad);
-  hipLaunchKernelGGL(k_ext_back, dim3(acs_grid(d.n, 256)), dim3(256), 0, s, d, st, Q, Vg, mk, cid, dc, pts, normp);
-  hipLaunchKernelGGL(k_ext_cam, dim3(1), dim3(64), 0, s, d, st, dc, cams, camnorm);
-  hipLaunchKernelGGL((k_ext_cost<G>), dim3(blocks), dim3(256), 0, s, d, st, 1, cams, pts, uv, mk, cid, Fp);
-  hipLaunchKernelGGL(k_ext_lm, dim3(1), dim3(256), 0, s, d, st, o, 0, Fp, normp, camnorm);
+// the starting state into both copies, the LM state (first: the rank round protocol's flag)
+static int ext_start(acs_ctx* ctx, const ExtDims& d, const ExtBuffers& b, const ObsSlots& in, double lambda0,
+                     int first) {
+  hipStream_t s = ctx->stream;
+  const size_t cam_bytes = sizeof(double) * ACS_CAM_STRIDE * d.C;
+  for (int k = 0; k < 2; ++k)
+    ACS_HIP(ctx, hipMemcpyAsync(b.cams + k * d.C * ACS_CAM_STRIDE, in.cams, cam_bytes, hipMemcpyDeviceToDevice, s));
+  ACS_HIP(ctx, hipMemcpyAsync(b.pts, in.pts, sizeof(double) * 3 * d.n, hipMemcpyDeviceToDevice, s));
+  ACS_HIP(ctx, hipMemsetAsync(b.bad, 0, sizeof(int), s));
+  ExtState st0;
+  std::memset(&st0, 0, sizeof(st0));
+  st0.lam = lambda0;
+  st0.relin = 1;
+  st0.first = first;
+  ACS_HIP(ctx, hipMemcpyAsync(b.st, &st0, sizeof(st0), hipMemcpyHostToDevice, s));
+  return ACS_OK;
+}
+
+// The launches every driver is made of (the single-GPU iteration, the rank phases, the first cost).
+// the system at the current state: slot records and point blocks, chunk partials
+static void ext_launch_system(hipStream_t s, const ExtDims& d, const ExtBuffers& b) {
+  const int blocks = acs_grid((int64_t)d.n * d.G, 256);
+#define EXT_LIN(g)                                                                                              \
+  hipLaunchKernelGGL((k_ext_linearize<g>), dim3(blocks), dim3(256), 0, s, d, b.st, b.cams, b.pts, b.uvp, b.mk, \
+                     b.cid, b.Q, b.Vg, b.Fp)
+  ACS_G_SWITCH(d.G, EXT_LIN)
+#undef EXT_LIN
+  hipLaunchKernelGGL(k_ext_schur, dim3(b.nchunk), dim3(256), ext_schur_lds(d, 3), s, d, b.st, b.Q, b.Vg, b.mk, b.cid,
+                     b.part);
+}
+
+static size_t ext_solve_lds(int C) {
+  const int NP = ((6 * C + 15) / 16) * 16;
+  return sizeof(double) * ((size_t)NP * (NP + 1) + NP + 512 + 256);
+}
+
+// the camera step from the nsys partial systems at sys (the point-gradient maximum from n_gp
+// points of Vg and n_slots per-rank values), the point steps, the trial cameras
+static void ext_launch_step(hipStream_t s, const ExtDims& d, const ExtBuffers& b, const double* sys, int nsys,
+                            int n_gp, const double* slots, int n_slots) {
+  hipLaunchKernelGGL(k_ext_solve, dim3(1), dim3(256), ext_solve_lds(d.C), s, d, b.st, nsys, sys, b.Vg, n_gp, slots,
+                     n_slots, b.dc, b.Sg, b.bad);
+  hipLaunchKernelGGL(k_ext_back, dim3(acs_grid(d.n, 256)), dim3(256), 0, s, d, b.st, b.Q, b.Vg, b.mk, b.cid, b.dc, b.pts,
+                     b.normp);
+  hipLaunchKernelGGL(k_ext_cam, dim3(1), dim3(64), 0, s, d, b.st, b.dc, b.cams, b.camnorm);
+}
+
+// the robust cost per point: which = 0 at the current state, 1 at the trial
+static void ext_launch_cost(hipStream_t s, const ExtDims& d, const ExtBuffers& b, int which) {
+  const int blocks = acs_grid((int64_t)d.n * d.G, 256);
+#define EXT_COST(g)                                                                                            \
+  hipLaunchKernelGGL((k_ext_cost<g>), dim3(blocks), dim3(256), 0, s, d, b.st, which, b.cams, b.pts, b.uvp, b.mk, \
+                     b.cid, b.Fp)
+  ACS_G_SWITCH(d.G, EXT_COST)
+#undef EXT_COST
+}
+
+// one LM iteration of the single-GPU solve
+static void ext_enqueue(hipStream_t s, const ExtDims& d, const ExtOpts& o, const ExtBuffers& b) {
+  ext_launch_system(s, d, b);
+  ext_launch_step(s, d, b, b.part, b.nchunk, d.n, nullptr, 0);
+  ext_launch_cost(s, d, b, 1);
+  hipLaunchKernelGGL(k_ext_lm, dim3(1), dim3(256), 0, s, d, b.st, o, 0, b.Fp, b.normp, b.camnorm);
+}
+
+static void ext_report(acs_sba_ext_report* report, const ExtState& hs, int nbad) {
+  report->status = hs.status == 0 ? ACS_STATUS_MAXITER : hs.status;
+  report->iters = hs.iters;
+  report->n_accepted = hs.nacc;
+  report->n_bad_pivots = nbad;
+  report->cost_before = hs.F0;
+  report->cost_after = hs.F;
+  report->grad_max = hs.gmax;
+  report->lambda_final = hs.lam;
 }
 
 extern "C" {
@@ -511,88 +557,37 @@ int acs_sba_extrinsics(acs_ctx* ctx, double* cams, int32_t n_cams, const double*
   ACS_CHECK(ctx, n_obs >= 1 && n_pts >= 1 && n_obs < (int64_t)INT32_MAX, "acs_sba_extrinsics: bad sizes");
   ACS_CHECK(ctx, op.f_scale > 0 && op.max_iters >= 0, "acs_sba_extrinsics: bad options");
   hipStream_t s = ctx->stream;
-  void *dcam0, *duv, *dpi, *dci, *dp0;
   int rc;
-  if ((rc = acs_stage_in(ctx, WS_CAMS, cams, sizeof(double) * ACS_CAM_STRIDE * n_cams, flags, &dcam0))) return rc;
-  if ((rc = acs_stage_in(ctx, WS_UV, uv, sizeof(double) * 2 * n_obs, flags, &duv))) return rc;
-  if ((rc = acs_stage_in(ctx, WS_PTIDX, pt_idx, sizeof(int32_t) * n_obs, flags, &dpi))) return rc;
-  if ((rc = acs_stage_in(ctx, WS_CAMIDX, cam_idx, sizeof(int32_t) * n_obs, flags, &dci))) return rc;
-  if ((rc = acs_stage_in(ctx, WS_PTS, pts, sizeof(double) * 3 * n_pts, flags, &dp0))) return rc;
+  ObsSlots in;
+  if ((rc = acs_stage_obs(ctx, "acs_sba_extrinsics", EXT_MAXK, ACS_CAM_STRIDE, cams, n_cams, uv, pt_idx, cam_idx, n_obs,
+                          pts, n_pts, flags, &in)))
+    return rc;
   double* drb = nullptr;
   if (resid_before) {
     drb = (double*)acs_out_buf(ctx, WS_OUT0, resid_before, sizeof(double) * 2 * n_obs, flags);
-    if (!drb || (rc = acs_sba_residuals(ctx, (const double*)dcam0, n_cams, (const double*)duv, (const int32_t*)dpi,
-                                        (const int32_t*)dci, n_obs, (const double*)dp0, n_pts, drb, ACS_DEVICE_PTRS)))
+    if (!drb || (rc = acs_sba_residuals(ctx, in.cams, n_cams, in.uv, in.pt_idx, in.cam_idx, n_obs, in.pts, n_pts, drb,
+                                        ACS_DEVICE_PTRS)))
       return rc ? rc : ACS_E_NOMEM;
   }
-  double2* uvp;
-  uint8_t *mk, *cid;
-  int K;
-  if ((rc = acs_obs_to_slots(ctx, (const double*)duv, (const int32_t*)dpi, (const int32_t*)dci, n_obs, n_pts, n_cams,
-                             &uvp, &mk, &cid, &K)))
-    return rc;
-  ACS_CHECK(ctx, K <= 64, "acs_sba_extrinsics: a point has %d observations (max 64)", K);
-  ExtDims d{(int)n_pts, K, n_cams, 2, EXT_CHUNK, op.f_scale * op.f_scale};
-  int G = 2;
-  while (G < K) G <<= 1;
-  d.G = G;
-  d.chunk = ext_chunk_points(K);
-  const int nchunk = (int)((n_pts + d.chunk - 1) / d.chunk);
-  const int NC = 6 * n_cams, nE = NC * NC + 3 * NC;
-  size_t off = 0;
-  auto take = [&](size_t cnt) {
-    size_t o = off;
-    off += ((cnt * sizeof(double) + 255) / 256) * 256 / sizeof(double);
-    return o;
-  };
-  const size_t oC = take(2 * (size_t)n_cams * ACS_CAM_STRIDE), oP = take(6 * (size_t)n_pts),
-               oQ = take((size_t)n_pts * K * EXT_Q), oV = take((size_t)n_pts * 10), oF = take(n_pts),
-               oPart = take((size_t)nchunk * nE), odc = take(96), oSg = take(96 * 96), onp = take(2 * (size_t)n_pts), ocn = take(64),
-               ost = take(16), obad = take(2);
-  double* arena = (double*)acs_ws(ctx, WS_FTE6, off * sizeof(double));
+  const ExtDims d = ext_dims(n_pts, in.K, n_cams, op.f_scale);
+  ExtBuffers b;
+  double* arena = (double*)acs_ws(ctx, WS_FTE6, ext_layout(b, nullptr, d, false));
   if (!arena) return ACS_E_NOMEM;
-  double *dcams = arena + oC, *dpts = arena + oP, *Q = arena + oQ, *Vg = arena + oV, *Fp = arena + oF,
-         *part = arena + oPart, *dc = arena + odc, *Sg = arena + oSg, *normp = arena + onp, *camnorm = arena + ocn;
-  ExtState* st = (ExtState*)(arena + ost);
-  int* bad = (int*)(arena + obad);
-  ACS_HIP(ctx, hipMemcpyAsync(dcams, dcam0, sizeof(double) * ACS_CAM_STRIDE * n_cams, hipMemcpyDeviceToDevice, s));
-  ACS_HIP(ctx, hipMemcpyAsync(dcams + n_cams * ACS_CAM_STRIDE, dcam0, sizeof(double) * ACS_CAM_STRIDE * n_cams,
-                              hipMemcpyDeviceToDevice, s));
-  ACS_HIP(ctx, hipMemcpyAsync(dpts, dp0, sizeof(double) * 3 * n_pts, hipMemcpyDeviceToDevice, s));
-  ACS_HIP(ctx, hipMemsetAsync(bad, 0, sizeof(int), s));
-  ExtState st0;
-  std::memset(&st0, 0, sizeof(st0));
-  st0.lam = op.lambda0;
-  st0.relin = 1;
-  ACS_HIP(ctx, hipMemcpyAsync(st, &st0, sizeof(st0), hipMemcpyHostToDevice, s));
+  ext_layout(b, arena, d, false);
+  b.uvp = in.uvp;
+  b.mk = in.mask;
+  b.cid = in.camid;
+  if ((rc = ext_start(ctx, d, b, in, op.lambda0, 0))) return rc;
   ExtOpts o{op.max_iters, op.ftol, op.xtol, op.gtol};
-  const int blocks = acs_grid((int64_t)n_pts * G, 256);
-  auto launch_cost0 = [&]() {
-    switch (G) {
-#define EXT_C0(g) \
-  case g: hipLaunchKernelGGL((k_ext_cost<g>), dim3(blocks), dim3(256), 0, s, d, st, 0, dcams, dpts, uvp, mk, cid, Fp); break;
-      EXT_C0(2) EXT_C0(4) EXT_C0(8) EXT_C0(16) EXT_C0(32) EXT_C0(64)
-#undef EXT_C0
-    }
-  };
-  launch_cost0();
-  hipLaunchKernelGGL(k_ext_lm, dim3(1), dim3(256), 0, s, d, st, o, 1, Fp, normp, camnorm);
+  ext_launch_cost(s, d, b, 0);
+  hipLaunchKernelGGL(k_ext_lm, dim3(1), dim3(256), 0, s, d, b.st, o, 1, b.Fp, b.normp, b.camnorm);
   ACS_HIP(ctx, hipGetLastError());
-  auto enqueue = [&]() {
-    switch (G) {
-#define EXT_IT(g) \
-  case g: ext_enqueue<g>(s, d, st, o, dcams, dpts, uvp, mk, cid, Q, Vg, Fp, part, dc, Sg, normp, camnorm, bad, nchunk); \
-    break;
-      EXT_IT(2) EXT_IT(4) EXT_IT(8) EXT_IT(16) EXT_IT(32) EXT_IT(64)
-#undef EXT_IT
-    }
-  };
   const int chunk = 4;
   hipGraph_t graph = nullptr;
   hipGraphExec_t exec = nullptr;
   bool use_graph = op.max_iters > 0 && hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed) == hipSuccess;
   if (use_graph) {
-    for (int c = 0; c < chunk; ++c) enqueue();
+    for (int c = 0; c < chunk; ++c) ext_enqueue(s, d, o, b);
     if (hipStreamEndCapture(s, &graph) != hipSuccess ||
         hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) {
       if (graph) (void)hipGraphDestroy(graph);
@@ -608,26 +603,26 @@ int acs_sba_extrinsics(acs_ctx* ctx, double* cams, int32_t n_cams, const double*
     if (use_graph) {
       ACS_HIP(ctx, hipGraphLaunch(exec, s));
     } else {
-      for (int c = 0; c < chunk; ++c) enqueue();
+      for (int c = 0; c < chunk; ++c) ext_enqueue(s, d, o, b);
     }
     ACS_HIP(ctx, hipGetLastError());
-    ACS_HIP(ctx, hipMemcpyAsync(&hs, st, sizeof(hs), hipMemcpyDeviceToHost, s));
+    ACS_HIP(ctx, hipMemcpyAsync(&hs, b.st, sizeof(hs), hipMemcpyDeviceToHost, s));
     ACS_HIP(ctx, hipStreamSynchronize(s));
     if (hs.status != 0) break;
   }
   if (exec) (void)hipGraphExecDestroy(exec);
   if (graph) (void)hipGraphDestroy(graph);
   if (op.max_iters == 0) {
-    ACS_HIP(ctx, hipMemcpyAsync(&hs, st, sizeof(hs), hipMemcpyDeviceToHost, s));
+    ACS_HIP(ctx, hipMemcpyAsync(&hs, b.st, sizeof(hs), hipMemcpyDeviceToHost, s));
     ACS_HIP(ctx, hipStreamSynchronize(s));
   }
-  const double* fcams = dcams + hs.cur * n_cams * ACS_CAM_STRIDE;
-  const double* fpts = dpts + (size_t)hs.cur * n_pts * 3;
+  const double* fcams = b.cams + hs.cur * n_cams * ACS_CAM_STRIDE;
+  const double* fpts = b.pts + (size_t)hs.cur * n_pts * 3;
   const hipMemcpyKind kout = (flags & ACS_DEVICE_PTRS) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
   if (resid_after) {
     double* dra = (double*)acs_out_buf(ctx, WS_OUT1, resid_after, sizeof(double) * 2 * n_obs, flags);
-    if (!dra || (rc = acs_sba_residuals(ctx, fcams, n_cams, (const double*)duv, (const int32_t*)dpi,
-                                        (const int32_t*)dci, n_obs, fpts, n_pts, dra, ACS_DEVICE_PTRS)))
+    if (!dra || (rc = acs_sba_residuals(ctx, fcams, n_cams, in.uv, in.pt_idx, in.cam_idx, n_obs, fpts, n_pts, dra,
+                                        ACS_DEVICE_PTRS)))
       return rc ? rc : ACS_E_NOMEM;
     if ((rc = acs_stage_out(ctx, resid_after, dra, sizeof(double) * 2 * n_obs, flags))) return rc;
   }
@@ -635,18 +630,9 @@ int acs_sba_extrinsics(acs_ctx* ctx, double* cams, int32_t n_cams, const double*
   ACS_HIP(ctx, hipMemcpyAsync(cams, fcams, sizeof(double) * ACS_CAM_STRIDE * n_cams, kout, s));
   ACS_HIP(ctx, hipMemcpyAsync(pts, fpts, sizeof(double) * 3 * n_pts, kout, s));
   int nbad = 0;
-  ACS_HIP(ctx, hipMemcpyAsync(&nbad, bad, sizeof(int), hipMemcpyDeviceToHost, s));
+  ACS_HIP(ctx, hipMemcpyAsync(&nbad, b.bad, sizeof(int), hipMemcpyDeviceToHost, s));
   ACS_HIP(ctx, hipStreamSynchronize(s));
-  if (report) {
-    report->status = hs.status == 0 ? ACS_STATUS_MAXITER : hs.status;
-    report->iters = hs.iters;
-    report->n_accepted = hs.nacc;
-    report->n_bad_pivots = nbad;
-    report->cost_before = hs.F0;
-    report->cost_after = hs.F;
-    report->grad_max = hs.gmax;
-    report->lambda_final = hs.lam;
-  }
+  if (report) ext_report(report, hs, nbad);
   return ACS_OK;
 }
 
@@ -709,7 +695,7 @@ __global__ __launch_bounds__(256) void k_ext_pack3(ExtDims d, const ExtState* __
 }
 
 // Rank round protocol: the decision on the pending trial from the all-reduced (cost,
-// |dX|^2, |X|^2) of the previous round (k_ext_lm's rule); a rejection marks the round
+// |dX|^2, |X|^2) of the previous round (ext_lm_decide); a rejection marks the round
 // SKIP (no step: the system is re-formed at the current state with the raised damping).
 __global__ void k_ext_decide(ExtDims d, ExtState* __restrict__ st, ExtOpts o, const double* __restrict__ p3,
                              const double* __restrict__ camnorm) {
@@ -722,37 +708,7 @@ __global__ void k_ext_decide(ExtDims d, ExtState* __restrict__ st, ExtOpts o, co
   }
   if (st->status != 0 || !st->pending) return;
   st->pending = 0;
-  double dn = p3[1], xn = p3[2];
-  for (int c = 0; c < d.C; ++c) {
-    dn += camnorm[2 * c];
-    xn += camnorm[2 * c + 1];
-  }
-  if (st->gmax <= o.gtol) {
-    st->status = ACS_STATUS_GTOL;
-    return;
-  }
-  const double f = p3[0];
-  st->iters += 1;
-  st->dnorm = sqrt(dn);
-  st->xnorm = sqrt(xn);
-  const bool small = sqrt(dn) <= o.xtol * (o.xtol + sqrt(xn));
-  if (f < st->F) {
-    const bool fconv = (st->F - f) <= o.ftol * fabs(st->F);
-    st->nacc += 1;
-    st->F = f;
-    st->cur ^= 1;
-    st->lam = fmax(st->lam * 0.1, EXT_LAM_MIN);
-    st->relin = 1;
-    if (fconv)
-      st->status = ACS_STATUS_FTOL;
-    else if (small)
-      st->status = ACS_STATUS_XTOL;
-  } else {
-    st->lam *= 10.0;
-    st->relin = 0;
-    if (st->lam > 1e16) st->status = ACS_STATUS_STALLED;
-  }
-  if (st->status == 0 && st->iters >= o.max_iters) st->status = ACS_STATUS_MAXITER;
+  ext_lm_decide(d, st, o, p3[0], p3[1], p3[2], camnorm);
   if (st->status == 0 && !st->relin) st->status = EXT_STATUS_SKIP;
 }
 
@@ -790,43 +746,13 @@ struct acs_sba_ext_dist {
   void* own = nullptr;
   ExtDims d;
   ExtOpts o;
-  int R, rank, nchunk;
-  double *dcams, *dpts, *Q, *Vg, *Fp, *part, *dc, *Sg, *normp, *camnorm;
-  double2* uvp;
-  uint8_t *mk, *cid;
-  ExtState* st;
-  int* bad;
+  int R, rank;
+  ExtBuffers b;
   // status after each round: pinned ring with completion events (acs_sba_ext_dist_poll)
   int32_t* snap = nullptr;
   hipEvent_t snap_ev[EXT_DIST_RING] = {};
   int64_t rounds = 0;
 };
-
-template <int G>
-static void ext_dist_linearize(acs_sba_ext_dist* h, hipStream_t s) {
-  const ExtDims& d = h->d;
-  const int blocks = acs_grid((int64_t)d.n * G, 256);
-  hipLaunchKernelGGL((k_ext_linearize<G>), dim3(blocks), dim3(256), 0, s, d, h->st, h->dcams, h->dpts, h->uvp, h->mk,
-                     h->cid, h->Q, h->Vg, h->Fp);
-}
-
-template <int G>
-static void ext_dist_cost(acs_sba_ext_dist* h, hipStream_t s, int which) {
-  const ExtDims& d = h->d;
-  const int blocks = acs_grid((int64_t)d.n * G, 256);
-  hipLaunchKernelGGL((k_ext_cost<G>), dim3(blocks), dim3(256), 0, s, d, h->st, which, h->dcams, h->dpts, h->uvp,
-                     h->mk, h->cid, h->Fp);
-}
-
-#define EXT_G_SWITCH(G, CALL)                  \
-  switch (G) {                                 \
-    case 2: CALL(2); break;                    \
-    case 4: CALL(4); break;                    \
-    case 8: CALL(8); break;                    \
-    case 16: CALL(16); break;                  \
-    case 32: CALL(32); break;                  \
-    default: CALL(64); break;                  \
-  }
 
 extern "C" {
 
@@ -844,76 +770,29 @@ int acs_sba_ext_dist_create(acs_ctx* ctx, const double* cams, int32_t n_cams, co
   ACS_CHECK(ctx, op.f_scale > 0 && op.max_iters >= 0, "sba_ext_dist: bad options");
   ACS_CHECK(ctx, world >= 1 && rank >= 0 && rank < world, "sba_ext_dist: rank %d / world %d", rank, world);
   hipStream_t s = ctx->stream;
-  void *dcam0, *duv, *dpi, *dci, *dp0;
   int rc;
-  if ((rc = acs_stage_in(ctx, WS_CAMS, cams, sizeof(double) * ACS_CAM_STRIDE * n_cams, flags, &dcam0))) return rc;
-  if ((rc = acs_stage_in(ctx, WS_UV, uv, sizeof(double) * 2 * n_obs, flags, &duv))) return rc;
-  if ((rc = acs_stage_in(ctx, WS_PTIDX, pt_idx, sizeof(int32_t) * n_obs, flags, &dpi))) return rc;
-  if ((rc = acs_stage_in(ctx, WS_CAMIDX, cam_idx, sizeof(int32_t) * n_obs, flags, &dci))) return rc;
-  if ((rc = acs_stage_in(ctx, WS_PTS, pts, sizeof(double) * 3 * n_pts, flags, &dp0))) return rc;
-  double2* uvp;
-  uint8_t *mk, *cid;
-  int K;
-  if ((rc = acs_obs_to_slots(ctx, (const double*)duv, (const int32_t*)dpi, (const int32_t*)dci, n_obs, n_pts, n_cams,
-                             &uvp, &mk, &cid, &K)))
+  ObsSlots in;
+  if ((rc = acs_stage_obs(ctx, "sba_ext_dist", EXT_MAXK, ACS_CAM_STRIDE, cams, n_cams, uv, pt_idx, cam_idx, n_obs, pts,
+                          n_pts, flags, &in)))
     return rc;
-  ACS_CHECK(ctx, K <= 64, "sba_ext_dist: a point has %d observations (max 64)", K);
   acs_sba_ext_dist* h = new acs_sba_ext_dist();
   h->ctx = ctx;
-  ExtDims& d = h->d;
-  d = ExtDims{(int)n_pts, K, n_cams, 2, EXT_CHUNK, op.f_scale * op.f_scale};
-  while (d.G < K) d.G <<= 1;
-  d.chunk = ext_chunk_points(K);
-  h->nchunk = (int)((n_pts + d.chunk - 1) / d.chunk);
+  h->d = ext_dims(n_pts, in.K, n_cams, op.f_scale);
   h->R = world;
   h->rank = rank;
   h->o = ExtOpts{op.max_iters, op.ftol, op.xtol, op.gtol};
   const int NC = 6 * n_cams, nE = NC * NC + 3 * NC;
-  size_t off = 0;
-  auto take = [&](size_t cnt) {
-    size_t o = off;
-    off += ((cnt * sizeof(double) + 255) / 256) * 256 / sizeof(double);
-    return o;
-  };
-  const size_t oC = take(2 * (size_t)n_cams * ACS_CAM_STRIDE), oP = take(6 * (size_t)n_pts),
-               oQ = take((size_t)n_pts * K * EXT_Q), oV = take((size_t)n_pts * 10), oF = take(n_pts),
-               oPart = take((size_t)h->nchunk * nE), odc = take(96), oSg = take(96 * 96), onp = take(2 * (size_t)n_pts),
-               ocn = take(64), ost = take(16), obad = take(2), ouv = take(2 * (size_t)n_pts * K),
-               omk = take(((size_t)n_pts * K + 7) / 8), ocid = take(((size_t)n_pts * K + 7) / 8);
-  if (acs_dev_malloc(&h->own, off * sizeof(double)) != hipSuccess) {
+  ExtBuffers& b = h->b;
+  if (acs_dev_malloc(&h->own, ext_layout(b, nullptr, h->d, true)) != hipSuccess) {
     delete h;
     return acs_fail(ctx, ACS_E_NOMEM, "sba_ext_dist: allocation failed");
   }
-  double* a = (double*)h->own;
-  h->dcams = a + oC;
-  h->dpts = a + oP;
-  h->Q = a + oQ;
-  h->Vg = a + oV;
-  h->Fp = a + oF;
-  h->part = a + oPart;
-  h->dc = a + odc;
-  h->Sg = a + oSg;
-  h->normp = a + onp;
-  h->camnorm = a + ocn;
-  h->st = (ExtState*)(a + ost);
-  h->bad = (int*)(a + obad);
-  h->uvp = (double2*)(a + ouv);
-  h->mk = (uint8_t*)(a + omk);
-  h->cid = (uint8_t*)(a + ocid);
-  ACS_HIP(ctx, hipMemcpyAsync(h->uvp, uvp, sizeof(double2) * n_pts * K, hipMemcpyDeviceToDevice, s));
-  ACS_HIP(ctx, hipMemcpyAsync(h->mk, mk, (size_t)n_pts * K, hipMemcpyDeviceToDevice, s));
-  ACS_HIP(ctx, hipMemcpyAsync(h->cid, cid, (size_t)n_pts * K, hipMemcpyDeviceToDevice, s));
-  for (int b = 0; b < 2; ++b)
-    ACS_HIP(ctx, hipMemcpyAsync(h->dcams + b * n_cams * ACS_CAM_STRIDE, dcam0, sizeof(double) * ACS_CAM_STRIDE * n_cams,
-                                hipMemcpyDeviceToDevice, s));
-  ACS_HIP(ctx, hipMemcpyAsync(h->dpts, dp0, sizeof(double) * 3 * n_pts, hipMemcpyDeviceToDevice, s));
-  ACS_HIP(ctx, hipMemsetAsync(h->bad, 0, sizeof(int), s));
-  ExtState st0;
-  std::memset(&st0, 0, sizeof(st0));
-  st0.lam = op.lambda0;
-  st0.relin = 1;
-  st0.first = 1;
-  ACS_HIP(ctx, hipMemcpyAsync(h->st, &st0, sizeof(st0), hipMemcpyHostToDevice, s));
+  ext_layout(b, (double*)h->own, h->d, true);
+  const size_t slots = (size_t)n_pts * in.K;
+  ACS_HIP(ctx, hipMemcpyAsync(b.uvp, in.uvp, sizeof(double2) * slots, hipMemcpyDeviceToDevice, s));
+  ACS_HIP(ctx, hipMemcpyAsync(b.mk, in.mask, slots, hipMemcpyDeviceToDevice, s));
+  ACS_HIP(ctx, hipMemcpyAsync(b.cid, in.camid, slots, hipMemcpyDeviceToDevice, s));
+  if ((rc = ext_start(ctx, h->d, b, in, op.lambda0, 1))) return rc;
   ACS_HIP(ctx, hipStreamSynchronize(s));
   bool snap_ok = acs_host_malloc((void**)&h->snap, sizeof(int32_t) * EXT_DIST_RING, hipHostMallocDefault) == hipSuccess;
   for (auto& e : h->snap_ev)
@@ -952,14 +831,11 @@ static int ext_dist_system(acs_sba_ext_dist* h, double* p1) {
   acs_ctx* ctx = h->ctx;
   hipStream_t s = ctx->stream;
   const ExtDims& d = h->d;
+  const ExtBuffers& b = h->b;
   const int NC = 6 * d.C, nE = NC * NC + 3 * NC;
   ACS_HIP(ctx, hipMemsetAsync(p1, 0, sizeof(double) * (nE + h->R), s));
-#define EXT_LIN(g) ext_dist_linearize<g>(h, s)
-  EXT_G_SWITCH(d.G, EXT_LIN)
-#undef EXT_LIN
-  hipLaunchKernelGGL(k_ext_schur, dim3(h->nchunk), dim3(256), ext_schur_lds(d), s, d, h->st, h->Q, h->Vg, h->mk,
-                     h->cid, h->part);
-  hipLaunchKernelGGL(k_ext_pack1, dim3(1), dim3(256), 0, s, d, h->st, h->nchunk, h->part, h->Vg, h->rank, p1);
+  ext_launch_system(s, d, b);
+  hipLaunchKernelGGL(k_ext_pack1, dim3(1), dim3(256), 0, s, d, b.st, b.nchunk, b.part, b.Vg, h->rank, p1);
   ACS_HIP(ctx, hipGetLastError());
   return ACS_OK;
 }
@@ -970,18 +846,11 @@ static int ext_dist_step(acs_sba_ext_dist* h, const double* p1, double* p3) {
   acs_ctx* ctx = h->ctx;
   hipStream_t s = ctx->stream;
   const ExtDims& d = h->d;
+  const ExtBuffers& b = h->b;
   const int NC = 6 * d.C, nE = NC * NC + 3 * NC;
-  const int NP = ((NC + 15) / 16) * 16;
-  const size_t lds_solve = sizeof(double) * ((size_t)NP * (NP + 1) + NP + 512 + 256);
-  hipLaunchKernelGGL(k_ext_solve, dim3(1), dim3(256), lds_solve, s, d, h->st, 1, p1, h->Vg, 0, p1 + nE, h->R, h->dc,
-                     h->Sg, h->bad);
-  hipLaunchKernelGGL(k_ext_back, dim3(acs_grid(d.n, 256)), dim3(256), 0, s, d, h->st, h->Q, h->Vg, h->mk, h->cid,
-                     h->dc, h->dpts, h->normp);
-  hipLaunchKernelGGL(k_ext_cam, dim3(1), dim3(64), 0, s, d, h->st, h->dc, h->dcams, h->camnorm);
-#define EXT_COST1(g) ext_dist_cost<g>(h, s, 1)
-  EXT_G_SWITCH(d.G, EXT_COST1)
-#undef EXT_COST1
-  hipLaunchKernelGGL(k_ext_pack3, dim3(1), dim3(256), 0, s, d, h->st, 1, h->Fp, h->normp, p3);
+  ext_launch_step(s, d, b, p1, 1, 0, p1 + nE, h->R);
+  ext_launch_cost(s, d, b, 1);
+  hipLaunchKernelGGL(k_ext_pack3, dim3(1), dim3(256), 0, s, d, b.st, 1, b.Fp, b.normp, p3);
   ACS_HIP(ctx, hipGetLastError());
   return ACS_OK;
 }
@@ -993,10 +862,8 @@ int acs_sba_ext_dist_init(acs_sba_ext_dist* h, double* payload) {
   ACS_DEVICE_GUARD(h ? h->ctx : nullptr);
   hipStream_t s = h->ctx->stream;
   const int NC = 6 * h->d.C, n1 = NC * NC + 3 * NC + h->R;
-#define EXT_COST0(g) ext_dist_cost<g>(h, s, 0)
-  EXT_G_SWITCH(h->d.G, EXT_COST0)
-#undef EXT_COST0
-  hipLaunchKernelGGL(k_ext_pack3, dim3(1), dim3(256), 0, s, h->d, h->st, 0, h->Fp, h->normp, payload + n1);
+  ext_launch_cost(s, h->d, h->b, 0);
+  hipLaunchKernelGGL(k_ext_pack3, dim3(1), dim3(256), 0, s, h->d, h->b.st, 0, h->b.Fp, h->b.normp, payload + n1);
   ACS_HIP(h->ctx, hipGetLastError());
   return ext_dist_system(h, payload);
 }
@@ -1011,14 +878,14 @@ int acs_sba_ext_dist_round(acs_sba_ext_dist* h, const double* in, double* out) {
   hipStream_t s = ctx->stream;
   const int NC = 6 * h->d.C, n1 = NC * NC + 3 * NC + h->R;
   int rc;
-  hipLaunchKernelGGL(k_ext_decide, dim3(1), dim3(64), 0, s, h->d, h->st, h->o, in + n1, (const double*)h->camnorm);
+  hipLaunchKernelGGL(k_ext_decide, dim3(1), dim3(64), 0, s, h->d, h->b.st, h->o, in + n1, (const double*)h->b.camnorm);
   if ((rc = ext_dist_step(h, in, out + n1))) return rc;
-  hipLaunchKernelGGL(k_ext_spec, dim3(1), dim3(64), 0, s, h->st, 1);
+  hipLaunchKernelGGL(k_ext_spec, dim3(1), dim3(64), 0, s, h->b.st, 1);
   if ((rc = ext_dist_system(h, out))) return rc;
-  hipLaunchKernelGGL(k_ext_spec, dim3(1), dim3(64), 0, s, h->st, 0);
+  hipLaunchKernelGGL(k_ext_spec, dim3(1), dim3(64), 0, s, h->b.st, 0);
   ACS_HIP(ctx, hipGetLastError());
   const int slot = (int)(h->rounds % EXT_DIST_RING);
-  ACS_HIP(ctx, hipMemcpyAsync(h->snap + slot, &h->st->status, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  ACS_HIP(ctx, hipMemcpyAsync(h->snap + slot, &h->b.st->status, sizeof(int32_t), hipMemcpyDeviceToHost, s));
   ACS_HIP(ctx, hipEventRecord(h->snap_ev[slot], s));
   h->rounds++;
   return ACS_OK;
@@ -1042,26 +909,17 @@ int acs_sba_ext_dist_result(acs_sba_ext_dist* h, double* cams, double* pts, acs_
   hipStream_t s = ctx->stream;
   const ExtDims& d = h->d;
   ExtState hs;
-  ACS_HIP(ctx, hipMemcpyAsync(&hs, h->st, sizeof(hs), hipMemcpyDeviceToHost, s));
+  ACS_HIP(ctx, hipMemcpyAsync(&hs, h->b.st, sizeof(hs), hipMemcpyDeviceToHost, s));
   ACS_HIP(ctx, hipStreamSynchronize(s));
   const hipMemcpyKind kout = (flags & ACS_DEVICE_PTRS) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
   if (cams)
-    ACS_HIP(ctx, hipMemcpyAsync(cams, h->dcams + hs.cur * d.C * ACS_CAM_STRIDE, sizeof(double) * ACS_CAM_STRIDE * d.C,
+    ACS_HIP(ctx, hipMemcpyAsync(cams, h->b.cams + hs.cur * d.C * ACS_CAM_STRIDE, sizeof(double) * ACS_CAM_STRIDE * d.C,
                                 kout, s));
-  if (pts) ACS_HIP(ctx, hipMemcpyAsync(pts, h->dpts + (size_t)hs.cur * d.n * 3, sizeof(double) * 3 * d.n, kout, s));
+  if (pts) ACS_HIP(ctx, hipMemcpyAsync(pts, h->b.pts + (size_t)hs.cur * d.n * 3, sizeof(double) * 3 * d.n, kout, s));
   int nbad = 0;
-  ACS_HIP(ctx, hipMemcpyAsync(&nbad, h->bad, sizeof(int), hipMemcpyDeviceToHost, s));
+  ACS_HIP(ctx, hipMemcpyAsync(&nbad, h->b.bad, sizeof(int), hipMemcpyDeviceToHost, s));
   ACS_HIP(ctx, hipStreamSynchronize(s));
-  if (report) {
-    report->status = hs.status == 0 ? ACS_STATUS_MAXITER : hs.status;
-    report->iters = hs.iters;
-    report->n_accepted = hs.nacc;
-    report->n_bad_pivots = nbad;
-    report->cost_before = hs.F0;
-    report->cost_after = hs.F;
-    report->grad_max = hs.gmax;
-    report->lambda_final = hs.lam;
-  }
+  if (report) ext_report(report, hs, nbad);
   return ACS_OK;
 }
 

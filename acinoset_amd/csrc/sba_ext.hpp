@@ -1,5 +1,6 @@
 // sba_ext.hpp — what the points + extrinsics SBA (sba_ext.hip) and its covariance
-// (sba_ext_cov.hip) share.
+// (sba_ext_cov.hip) share: the problem's dimensions, the slot record, an observation's blocks
+// (ext_obs_blocks) and the Schur partials (ext_schur_stage, ext_schur_entry).
 #pragma once
 
 #include <algorithm>
@@ -8,6 +9,35 @@
 
 #define EXT_MAXC 16
 #define EXT_CHUNK 64
+#define EXT_MAXK 64  // observations of one point: one 64-lane group, one slot per lane
+
+// The slot record, EXT_Q doubles per observation slot: U (21 packed upper), W = J_cam^T J_pt (6 x 3)
+// and, in the solver's record only (GC = true), the camera gradient g_c (6) behind them.
+enum : int { EXT_Q_U = 0, EXT_Q_W = 21, EXT_Q_GC = 39 };
+template <bool GC>
+constexpr int EXT_Q = GC ? 45 : 39;
+
+// n points of K slots, C cameras; one point = one aligned group of G lanes (ACS_G_SWITCH);
+// chunk: points per Schur block; f2 = f_scale^2
+struct ExtDims {
+  int n, K, C, G, chunk;
+  double f2;
+};
+
+// chunk: the W M tiles of a Schur block (18 doubles and a camera id per slot, 3 doubles per
+// point) must fit ~96 KB of LDS
+static inline ExtDims ext_dims(int64_t n_pts, int K, int n_cams, double f_scale) {
+  ExtDims d{(int)n_pts, K, n_cams, 2, 0, f_scale * f_scale};
+  while (d.G < K) d.G <<= 1;
+  d.chunk = std::max(1, std::min(EXT_CHUNK, (int)(96 * 1024 / (148 * K + 24))));
+  return d;
+}
+static inline int ext_nchunk(const ExtDims& d) { return (d.n + d.chunk - 1) / d.chunk; }
+
+// LDS of a Schur block: W M (18 doubles per slot), `per_point` doubles per point, a camera id per slot
+static inline size_t ext_schur_lds(const ExtDims& d, int per_point) {
+  return sizeof(double) * ((size_t)d.chunk * d.K * 18 + d.chunk * per_point) + sizeof(int) * (size_t)d.chunk * d.K;
+}
 
 __device__ __forceinline__ int upk(int i, int j) {  // packed upper-triangular index, 6x6
   if (i > j) {
@@ -18,6 +48,96 @@ __device__ __forceinline__ int upk(int i, int j) {  // packed upper-triangular i
   return i * 6 - i * (i - 1) / 2 + (j - i);
 }
 
-// points per Schur block: the W M tiles of a chunk (18 doubles and a camera id per slot, 3
-// doubles per point) must fit ~96 KB of LDS
-static inline int ext_chunk_points(int K) { return std::max(1, std::min(EXT_CHUNK, (int)(96 * 1024 / (148 * K + 24)))); }
+// One observation at the camera record c (LDS) of the point X with the measurement m, per image
+// row dd: the residual r, the Cauchy weight w = 1 / (1 + z), z = r^2 / f2, the Triggs weight
+// wh = max((1 - z) w^2, 0.1 w), J_cam = [-(J_Y [v]x) | J_Y] with v = R X = Y - t, and
+// J_pt = J_Y R.
+struct ExtObs {
+  double r[2], z[2], w[2], wh[2], jc[2][6], jp[2][3];
+};
+// ... and its camera-side blocks U = sum_dd wh J_cam^T J_cam (packed) and W = sum_dd wh J_cam^T J_pt,
+// written to the slot record q
+__device__ __forceinline__ void ext_obs_blocks(const double* c, double X0, double X1, double X2, double2 m, double f2,
+                                               ExtObs& ob, double* q) {
+  double U[21], W[18];
+  for (int e = 0; e < 21; ++e) U[e] = 0.0;
+  for (int e = 0; e < 18; ++e) W[e] = 0.0;
+  ProjOut po;
+  fisheye_project<true>(c, X0, X1, X2, po);
+  ob.r[0] = po.u - m.x;
+  ob.r[1] = po.v - m.y;
+  const double v0 = po.Y[0] - c[17], v1 = po.Y[1] - c[18], v2 = po.Y[2] - c[19];
+  for (int dd = 0; dd < 2; ++dd) {
+    const double* jy = po.JY + 3 * dd;
+    double* jc = ob.jc[dd];
+    double* jp = ob.jp[dd];
+    jc[0] = -(jy[1] * v2 - jy[2] * v1);
+    jc[1] = -(jy[2] * v0 - jy[0] * v2);
+    jc[2] = -(jy[0] * v1 - jy[1] * v0);
+    for (int i = 0; i < 3; ++i) {
+      jc[3 + i] = jy[i];
+      jp[i] = po.J[3 * dd + i];
+    }
+    const double z = ob.r[dd] * ob.r[dd] / f2;
+    const double w = 1.0 / (1.0 + z);
+    const double wh = fmax((1.0 - z) * w * w, 0.1 * w);
+    ob.z[dd] = z;
+    ob.w[dd] = w;
+    ob.wh[dd] = wh;
+    for (int i = 0; i < 6; ++i) {
+      for (int j = i; j < 6; ++j) U[upk(i, j)] += wh * jc[i] * jc[j];
+      for (int j = 0; j < 3; ++j) W[i * 3 + j] += wh * jc[i] * jp[j];
+    }
+  }
+  for (int e = 0; e < 21; ++e) q[EXT_Q_U + e] = U[e];
+  for (int e = 0; e < 18; ++e) q[EXT_Q_W + e] = W[e];
+}
+
+// The Schur partial of a chunk of np points from p0, S = sum U - sum W M W^T, in two steps.
+// ext_schur_stage: every point's W M tiles (sZ, np x K x 18) and camera ids (scam, np x K, -1 = no
+// observation or a point that takes no part) into LDS. point_m(p, t, M) gives point p (t-th of
+// the chunk) its 3x3 M and returns whether it takes part. Ends with a barrier.
+template <bool GC, class PointM>
+__device__ __forceinline__ void ext_schur_stage(const ExtDims& d, int p0, int np, const double* __restrict__ Q,
+                                                const uint8_t* __restrict__ mask,
+                                                const uint8_t* __restrict__ camid, double* sZ, int* scam,
+                                                PointM point_m) {
+  for (int t = threadIdx.x; t < np; t += blockDim.x) {
+    const int p = p0 + t;
+    double M[9];
+    const bool pok = point_m(p, t, M);
+    for (int s = 0; s < d.K; ++s) {
+      const int64_t o = (int64_t)p * d.K + s;
+      const bool ok = pok && mask[o] && camid[o] < d.C;
+      scam[t * d.K + s] = ok ? camid[o] : -1;
+      const double* W = Q + (size_t)o * EXT_Q<GC> + EXT_Q_W;
+      for (int i = 0; i < 6; ++i)
+        for (int j = 0; j < 3; ++j)
+          sZ[((size_t)t * d.K + s) * 18 + i * 3 + j] =
+              ok ? W[i * 3] * M[j] + W[i * 3 + 1] * M[3 + j] + W[i * 3 + 2] * M[6 + j] : 0.0;
+    }
+  }
+  __syncthreads();
+}
+
+// ext_schur_entry: entry (a, b) of S over the chunk, summed in point and slot order by one thread
+template <bool GC>
+__device__ __forceinline__ double ext_schur_entry(const ExtDims& d, int p0, int np, const double* __restrict__ Q,
+                                                  const double* sZ, const int* scam, int a, int b) {
+  const int c1 = a / 6, k1 = a % 6, c2 = b / 6, k2 = b % 6;
+  double acc = 0.0;
+  for (int t = 0; t < np; ++t) {
+    const int64_t base = (int64_t)(p0 + t) * d.K;
+    for (int s1 = 0; s1 < d.K; ++s1) {
+      if (scam[t * d.K + s1] != c1) continue;
+      if (c1 == c2) acc += Q[(size_t)(base + s1) * EXT_Q<GC> + EXT_Q_U + upk(k1, k2)];
+      const double* z = sZ + ((size_t)t * d.K + s1) * 18 + k1 * 3;
+      for (int s2 = 0; s2 < d.K; ++s2) {
+        if (scam[t * d.K + s2] != c2) continue;
+        const double* w = Q + (size_t)(base + s2) * EXT_Q<GC> + EXT_Q_W + k2 * 3;
+        acc -= z[0] * w[0] + z[1] * w[1] + z[2] * w[2];
+      }
+    }
+  }
+  return acc;
+}

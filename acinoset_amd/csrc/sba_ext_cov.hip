@@ -3,8 +3,8 @@
 //
 // Definition (include/acinoset_hip.h), everything at the state passed in:
 //   per camera (dw, dt): R <- exp([dw]x) R, t <- t + dt; J_cam = J_Y [-[R X]x | I], J_pt = J_Y R;
-//   wh = max((1 - z) w^2, 0.1 w), w = 1 / (1 + z), z = r^2 / f_scale^2 (k_ext_linearize's).
-//   Point status on its own V = sum wh J_pt^T J_pt (k_sba_cov's rule); a point that is not OK is
+//   wh = max((1 - z) w^2, 0.1 w), w = 1 / (1 + z), z = r^2 / f_scale^2 (ext_obs_blocks, sba_ext.hpp).
+//   Point status on its own V = sum wh J_pt^T J_pt (cov_point_status); a point that is not OK is
 //   left out entirely. S = sum U - sum_OK W V^-1 W^T, undamped, symmetrised.
 //   Gauge generators G (6C x 7): rotation dw = -R_c theta; translation dt = -R_c tau; scale
 //   dt = t_c. Q = orth(G), mu = max diag S, Ah = S + mu Q Q^T scaled to unit diagonal.
@@ -15,11 +15,12 @@
 //   Point i: cov_i = sigma^2 V_i^-1 + V_i^-1 B_i^T cov_cc B_i V_i^-1.
 //
 // Kernels:
-//   k_extcov_linearize<G> [point groups] one point per aligned lane group (k_ext_linearize's
-//                   mapping): per slot U (21 packed) and W (18); per point V summed over the
-//                   group, its status, V^-1 (LDL^T, k_sba_cov's) and the sigma_hat terms
+//   k_extcov_linearize<G> [point groups] one point per aligned lane group (ACS_G_SWITCH): per
+//                   slot U (21 packed) and W (18) by ext_obs_blocks; per point V summed over the
+//                   group, V^-1 and its status (ldl3_inverse, cov_point_status; common.hpp) and
+//                   the sigma_hat terms
 //   k_extcov_schur  [point chunks] fixed-order chunk partials of S over the OK points
-//                   (k_ext_schur's scheme, no atomics)
+//                   (ext_schur_stage, ext_schur_entry with M = V^-1; no atomics)
 //   k_extcov_cams   [1 block] chunk sums in order, symmetrise, G and its Gram-Schmidt, mu,
 //                   Jacobi scaling, scalar LDL^T pivot test, SPD inverse on the f64 MFMA tiles
 //                   (wg_spd_inverse) with one refinement step, unscale, - Q Q^T / mu, anchor
@@ -29,16 +30,10 @@
 #include "mfma64.hpp"
 #include "sba_ext.hpp"
 
-#define XC_Q 39  // per slot: U (21 packed upper) + W (18)
-#define XC_PIVOT_TOL 1e-9
-
-struct XcDims {
-  int n, K, C, chunk;
-  double f2;
-};
+#define XC_PIVOT_TOL 1e-9  // pivots of the unit-diagonal reduced camera system (k_extcov_cams)
 
 template <int G>
-__global__ __launch_bounds__(256) void k_extcov_linearize(XcDims d, const double* __restrict__ cams,
+__global__ __launch_bounds__(256) void k_extcov_linearize(ExtDims d, const double* __restrict__ cams,
                                                           const double* __restrict__ pts,
                                                           const double2* __restrict__ uv,
                                                           const uint8_t* __restrict__ mask,
@@ -58,73 +53,35 @@ __global__ __launch_bounds__(256) void k_extcov_linearize(XcDims d, const double
   for (int i = 0; i < 8; ++i) v[i] = 0.0;
   for (int slot = lane; slot < d.K; slot += G) {
     const int64_t o = p * d.K + slot;
-    double* q = Q + (size_t)o * XC_Q;
+    double* q = Q + (size_t)o * EXT_Q<false>;
     if (!mask[o] || camid[o] >= d.C) {
-      for (int e = 0; e < XC_Q; ++e) q[e] = 0.0;
+      for (int e = 0; e < EXT_Q<false>; ++e) q[e] = 0.0;
       continue;
     }
-    const double* c = s_cam + camid[o] * ACS_CAM_STRIDE;
-    ProjOut po;
-    fisheye_project<true>(c, X0, X1, X2, po);
-    const double2 m = uv[o];
-    const double r[2] = {po.u - m.x, po.v - m.y};
-    // R X = Y - t
-    const double v0 = po.Y[0] - c[17], v1 = po.Y[1] - c[18], v2 = po.Y[2] - c[19];
-    double U[21], W[18];
-    for (int e = 0; e < 21; ++e) U[e] = 0.0;
-    for (int e = 0; e < 18; ++e) W[e] = 0.0;
+    ExtObs ob;
+    ext_obs_blocks(s_cam + camid[o] * ACS_CAM_STRIDE, X0, X1, X2, uv[o], d.f2, ob, q);
     for (int dd = 0; dd < 2; ++dd) {
-      const double* jy = po.JY + 3 * dd;
-      const double* jp = po.J + 3 * dd;
-      // J_cam = [-(J_Y [v]x), J_Y]
-      const double jc[6] = {-(jy[1] * v2 - jy[2] * v1), -(jy[2] * v0 - jy[0] * v2), -(jy[0] * v1 - jy[1] * v0),
-                            jy[0], jy[1], jy[2]};
-      const double rr = r[dd] * r[dd];
-      const double z = rr / d.f2;
-      const double w = 1.0 / (1.0 + z);
-      const double wh = fmax((1.0 - z) * w * w, 0.1 * w);
-      for (int i = 0; i < 6; ++i) {
-        for (int j = i; j < 6; ++j) U[upk(i, j)] += wh * jc[i] * jc[j];
-        for (int j = 0; j < 3; ++j) W[i * 3 + j] += wh * jc[i] * jp[j];
-      }
+      const double* jp = ob.jp[dd];
+      const double wh = ob.wh[dd];
       v[0] += wh * jp[0] * jp[0];
       v[1] += wh * jp[0] * jp[1];
       v[2] += wh * jp[0] * jp[2];
       v[3] += wh * jp[1] * jp[1];
       v[4] += wh * jp[1] * jp[2];
       v[5] += wh * jp[2] * jp[2];
-      v[6] += w * rr;
+      v[6] += ob.w[dd] * (ob.r[dd] * ob.r[dd]);
     }
     v[7] += 2.0;
-    for (int e = 0; e < 21; ++e) q[e] = U[e];
-    for (int e = 0; e < 18; ++e) q[21 + e] = W[e];
   }
 #pragma unroll
   for (int i = 0; i < 8; ++i) v[i] = group_sum<G>(v[i]);
   if (lane != 0) return;
-  // LDL^T without pivoting (k_sba_cov's): V^-1 = sum_k (1 / d_k) m_k^T m_k, m_k the rows of L^-1
-  const double d0 = v[0], i0 = 1.0 / d0;
-  const double l10 = v[1] * i0, l20 = v[2] * i0;
-  const double d1 = v[3] - l10 * v[1], i1 = 1.0 / d1;
-  const double t = v[4] - l20 * v[1];
-  const double l21 = t * i1;
-  const double d2 = v[5] - l20 * v[2] - l21 * t, i2 = 1.0 / d2;
-  const double thr = XC_PIVOT_TOL * fmax(v[0], fmax(v[3], v[5]));
-  const bool ok = d0 > thr && d1 > thr && d2 > thr;  // a NaN pivot or threshold fails
-  const int st = v[7] == 0.0 ? ACS_COV_NOOBS : ok ? ACS_COV_OK : ACS_COV_DEGENERATE;
+  double ci[6];
+  const bool ok = ldl3_inverse(v, [](double x) { return 1.0 / x; }, ci);
+  const int st = cov_point_status(v[7], ok);
   const bool good = st == ACS_COV_OK;
-  const double m20 = l10 * l21 - l20;
-  const double c22 = i2, c12 = -l21 * i2, c02 = m20 * i2;
-  const double c11 = i1 + l21 * l21 * i2;
-  const double c01 = -l10 * i1 - l21 * c02;
-  const double c00 = i0 + l10 * l10 * i1 + m20 * c02;
   double* vi = Vi + (size_t)p * 6;  // V^-1, packed upper; zeros for a point that is left out
-  vi[0] = good ? c00 : 0.0;
-  vi[1] = good ? c01 : 0.0;
-  vi[2] = good ? c02 : 0.0;
-  vi[3] = good ? c11 : 0.0;
-  vi[4] = good ? c12 : 0.0;
-  vi[5] = good ? c22 : 0.0;
+  for (int e = 0; e < 6; ++e) vi[e] = good ? ci[e] : 0.0;
   status[p] = st;
   wr2[p] = good ? v[6] : 0.0;
   nres[p] = good ? (int32_t)v[7] : 0;
@@ -132,7 +89,7 @@ __global__ __launch_bounds__(256) void k_extcov_linearize(XcDims d, const double
 
 // chunk partial of S (6C x 6C) over the OK points of the chunk, every entry summed in point and
 // slot order by one thread
-__global__ __launch_bounds__(256) void k_extcov_schur(XcDims d, const double* __restrict__ Q,
+__global__ __launch_bounds__(256) void k_extcov_schur(ExtDims d, const double* __restrict__ Q,
                                                       const double* __restrict__ Vi,
                                                       const int32_t* __restrict__ status,
                                                       const uint8_t* __restrict__ mask,
@@ -141,43 +98,16 @@ __global__ __launch_bounds__(256) void k_extcov_schur(XcDims d, const double* __
   const int p0 = ch * d.chunk, p1 = min(d.n, p0 + d.chunk), np = p1 - p0;
   const int NC = 6 * d.C, nE = NC * NC;
   extern __shared__ double lds[];
-  double* sZ = lds;                                   // np x K x 18  (W V^-1)
+  double* sZ = lds;                                     // np x K x 18  (W V^-1)
   int* scam = (int*)(sZ + (size_t)d.chunk * d.K * 18);  // np x K camera id (-1 = none / left out)
-  for (int t = threadIdx.x; t < np; t += blockDim.x) {
-    const int p = p0 + t;
+  ext_schur_stage<false>(d, p0, np, Q, mask, camid, sZ, scam, [&](int p, int, double* M) {
     const double* vi = Vi + (size_t)p * 6;
-    const double M[9] = {vi[0], vi[1], vi[2], vi[1], vi[3], vi[4], vi[2], vi[4], vi[5]};
-    const bool pok = status[p] == ACS_COV_OK;
-    for (int s = 0; s < d.K; ++s) {
-      const int64_t o = (int64_t)p * d.K + s;
-      const bool ok = pok && mask[o] && camid[o] < d.C;
-      scam[t * d.K + s] = ok ? camid[o] : -1;
-      const double* W = Q + (size_t)o * XC_Q + 21;
-      for (int i = 0; i < 6; ++i)
-        for (int j = 0; j < 3; ++j)
-          sZ[((size_t)t * d.K + s) * 18 + i * 3 + j] =
-              ok ? W[i * 3] * M[j] + W[i * 3 + 1] * M[3 + j] + W[i * 3 + 2] * M[6 + j] : 0.0;
-    }
-  }
-  __syncthreads();
-  for (int e = threadIdx.x; e < nE; e += blockDim.x) {
-    double acc = 0.0;
-    const int a = e / NC, b = e % NC, c1 = a / 6, k1 = a % 6, c2 = b / 6, k2 = b % 6;
-    for (int t = 0; t < np; ++t) {
-      const int64_t base = (int64_t)(p0 + t) * d.K;
-      for (int s1 = 0; s1 < d.K; ++s1) {
-        if (scam[t * d.K + s1] != c1) continue;
-        if (c1 == c2) acc += Q[(size_t)(base + s1) * XC_Q + upk(k1, k2)];
-        const double* z = sZ + ((size_t)t * d.K + s1) * 18 + k1 * 3;
-        for (int s2 = 0; s2 < d.K; ++s2) {
-          if (scam[t * d.K + s2] != c2) continue;
-          const double* w = Q + (size_t)(base + s2) * XC_Q + 21 + k2 * 3;
-          acc -= z[0] * w[0] + z[1] * w[1] + z[2] * w[2];
-        }
-      }
-    }
-    part[(size_t)ch * nE + e] = acc;
-  }
+    const double m[9] = {vi[0], vi[1], vi[2], vi[1], vi[3], vi[4], vi[2], vi[4], vi[5]};
+    for (int k = 0; k < 9; ++k) M[k] = m[k];
+    return status[p] == ACS_COV_OK;
+  });
+  for (int e = threadIdx.x; e < nE; e += blockDim.x)
+    part[(size_t)ch * nE + e] = ext_schur_entry<false>(d, p0, np, Q, sZ, scam, e / NC, e % NC);
 }
 
 // sum over the 64 lanes of a wave, the same bits in every lane
@@ -197,7 +127,7 @@ static size_t extcov_cams_lds(int NP) {
   return sizeof(double) * ((size_t)NP * (NP + 1) + 4 * (size_t)NP * 8 + NP + 512 + 256 + 128 + 1024);
 }
 
-__global__ __launch_bounds__(256) void k_extcov_cams(XcDims d, XcCamArgs ar, const double* __restrict__ part,
+__global__ __launch_bounds__(256) void k_extcov_cams(ExtDims d, XcCamArgs ar, const double* __restrict__ part,
                                                      const double* __restrict__ cams,
                                                      const int32_t* __restrict__ status,
                                                      const double* __restrict__ wr2, const int32_t* __restrict__ nres,
@@ -516,7 +446,7 @@ __global__ __launch_bounds__(256) void k_extcov_cams(XcDims d, XcCamArgs ar, con
 // The throughput path: one point per aligned lane group, lane l owns slot l. cov_cc (6C x 6C,
 // sigma^2 applied) is staged in LDS.
 template <int G>
-__global__ __launch_bounds__(256) void k_extcov_points(XcDims d, const double* __restrict__ covc,
+__global__ __launch_bounds__(256) void k_extcov_points(ExtDims d, const double* __restrict__ covc,
                                                        const double* __restrict__ Q, const double* __restrict__ Vi,
                                                        const int32_t* __restrict__ status,
                                                        const uint8_t* __restrict__ mask,
@@ -537,13 +467,13 @@ __global__ __launch_bounds__(256) void k_extcov_points(XcDims d, const double* _
       const int64_t o = p * d.K + slot;
       if (!mask[o] || camid[o] >= d.C) continue;
       const int co = camid[o];
-      const double* Wo = Q + (size_t)o * XC_Q + 21;
+      const double* Wo = Q + (size_t)o * EXT_Q<false> + EXT_Q_W;
       double T[18];
       for (int e = 0; e < 18; ++e) T[e] = 0.0;
       for (int s = 0; s < d.K; ++s) {
         const int64_t o2 = p * d.K + s;
         if (!mask[o2] || camid[o2] >= d.C) continue;
-        const double* W2 = Q + (size_t)o2 * XC_Q + 21;
+        const double* W2 = Q + (size_t)o2 * EXT_Q<false> + EXT_Q_W;
         const double* blk = s_cc + (size_t)(6 * co) * NC + 6 * camid[o2];
         for (int k = 0; k < 6; ++k) {
           const double w0 = W2[k * 3], w1 = W2[k * 3 + 1], w2 = W2[k * 3 + 2];
@@ -586,16 +516,6 @@ __global__ __launch_bounds__(256) void k_extcov_points(XcDims d, const double* _
   double* c = covp + 9 * p;
   for (int e = 0; e < 9; ++e) c[e] = out[e];
 }
-
-#define XC_G_SWITCH(G, CALL) \
-  switch (G) {               \
-    case 2: CALL(2); break;  \
-    case 4: CALL(4); break;  \
-    case 8: CALL(8); break;  \
-    case 16: CALL(16); break; \
-    case 32: CALL(32); break; \
-    default: CALL(64); break; \
-  }
 
 extern "C" {
 
@@ -657,38 +577,31 @@ int acs_sba_extrinsics_covariance(acs_ctx* ctx, const double* cams, int32_t n_ca
     ACS_CHECK(ctx, d2 > 1e-24 * (sc2 > 1.0 ? sc2 : 1.0),
               "acs_sba_extrinsics_covariance: the centres of cameras %d and %d coincide", op.anchor_cam, op.scale_cam);
   }
-  void *dcam, *duv, *dpi, *dci, *dp;
   int rc;
-  if ((rc = acs_stage_in(ctx, WS_CAMS, cams, sizeof(double) * ACS_CAM_STRIDE * n_cams, flags, &dcam))) return rc;
-  if ((rc = acs_stage_in(ctx, WS_UV, uv, sizeof(double) * 2 * n_obs, flags, &duv))) return rc;
-  if ((rc = acs_stage_in(ctx, WS_PTIDX, pt_idx, sizeof(int32_t) * n_obs, flags, &dpi))) return rc;
-  if ((rc = acs_stage_in(ctx, WS_CAMIDX, cam_idx, sizeof(int32_t) * n_obs, flags, &dci))) return rc;
-  if ((rc = acs_stage_in(ctx, WS_PTS, pts, sizeof(double) * 3 * n_pts, flags, &dp))) return rc;
-  double2* uvp;
-  uint8_t *mk, *cid;
-  int K;
-  if ((rc = acs_obs_to_slots(ctx, (const double*)duv, (const int32_t*)dpi, (const int32_t*)dci, n_obs, n_pts, n_cams,
-                             &uvp, &mk, &cid, &K))) {
-    // the shared slot builder words its errors for acs_sba_points: name this entry point
-    ctx->err = "acs_sba_extrinsics_covariance: " + ctx->err;
+  ObsSlots in;
+  if ((rc = acs_stage_obs(ctx, "acs_sba_extrinsics_covariance", EXT_MAXK, ACS_CAM_STRIDE, cams, n_cams, uv, pt_idx,
+                          cam_idx, n_obs, pts, n_pts, flags, &in)))
     return rc;
-  }
-  ACS_CHECK(ctx, K <= 64, "acs_sba_extrinsics_covariance: a point has %d observations (max 64)", K);
-  XcDims d{(int)n_pts, K, n_cams, ext_chunk_points(K), op.f_scale * op.f_scale};
-  int G = 2;
-  while (G < K) G <<= 1;
-  const int nchunk = (int)((n_pts + d.chunk - 1) / d.chunk);
+  const ExtDims d = ext_dims(n_pts, in.K, n_cams, op.f_scale);
+  const int nchunk = ext_nchunk(d);
   const int NC = 6 * n_cams, NP = ((NC + 15) / 16) * 16, nE = NC * NC;
-  size_t off = 0;
-  auto take = [&](size_t cnt) {
-    size_t o = off;
-    off += ((cnt * sizeof(double) + 255) / 256) * 256 / sizeof(double);
-    return o;
+  double *Q, *Vi, *wr2, *part, *Ag, *T1, *T2;
+  int32_t* nres;
+  int* bad;
+  auto layout = [&](double* base) {
+    Arena a{base};
+    Q = a.take((size_t)n_pts * d.K * EXT_Q<false>);
+    Vi = a.take((size_t)n_pts * 6);
+    wr2 = a.take(n_pts);
+    nres = a.take<int32_t>(((size_t)n_pts + 1) / 2);
+    part = a.take((size_t)nchunk * nE);
+    Ag = a.take((size_t)NP * NP);
+    T1 = a.take((size_t)NP * NP);
+    T2 = a.take((size_t)NP * NP);
+    bad = a.take<int>(2);
+    return a.bytes();
   };
-  const size_t oQ = take((size_t)n_pts * K * XC_Q), oV = take((size_t)n_pts * 6), oW = take(n_pts),
-               oN = take(((size_t)n_pts + 1) / 2), oPart = take((size_t)nchunk * nE), oA = take((size_t)NP * NP),
-               oT1 = take((size_t)NP * NP), oT2 = take((size_t)NP * NP), obad = take(2);
-  double* arena = (double*)acs_ws(ctx, WS_FTE7, off * sizeof(double));
+  double* arena = (double*)acs_ws(ctx, WS_FTE7, layout(nullptr));
   double* dcc = (double*)acs_out_buf(ctx, WS_OUT0, cov_cams, sizeof(double) * nE, flags);
   // without cov_pts the point kernel is not run; the status is needed by the camera kernel anyway
   double* dcp = cov_pts ? (double*)acs_out_buf(ctx, WS_OUT1, cov_pts, sizeof(double) * 9 * n_pts, flags) : nullptr;
@@ -696,32 +609,25 @@ int acs_sba_extrinsics_covariance(acs_ctx* ctx, const double* cams, int32_t n_ca
                                        pt_status ? flags : (flags & ~ACS_DEVICE_PTRS));
   acs_sba_ext_cov_report* drep = (acs_sba_ext_cov_report*)acs_ws(ctx, WS_REPORT, sizeof(acs_sba_ext_cov_report));
   if (!arena || !dcc || (cov_pts && !dcp) || !dst || !drep) return ACS_E_NOMEM;
-  double *Q = arena + oQ, *Vi = arena + oV, *wr2 = arena + oW, *part = arena + oPart, *Ag = arena + oA,
-         *T1 = arena + oT1, *T2 = arena + oT2;
-  int32_t* nres = (int32_t*)(arena + oN);
-  int* bad = (int*)(arena + obad);
+  layout(arena);
   ACS_HIP(ctx, hipMemsetAsync(bad, 0, sizeof(int), s));
-  const int blocks = acs_grid((int64_t)n_pts * G, 256);
-#define XC_LIN(g)                                                                                              \
-  hipLaunchKernelGGL((k_extcov_linearize<g>), dim3(blocks), dim3(256), 0, s, d, (const double*)dcam,           \
-                     (const double*)dp, (const double2*)uvp, (const uint8_t*)mk, (const uint8_t*)cid, Q, Vi, dst, \
-                     wr2, nres)
-  XC_G_SWITCH(G, XC_LIN)
+  const int blocks = acs_grid((int64_t)n_pts * d.G, 256);
+#define XC_LIN(g)                                                                                                  \
+  hipLaunchKernelGGL((k_extcov_linearize<g>), dim3(blocks), dim3(256), 0, s, d, in.cams, in.pts, in.uvp, in.mask, \
+                     in.camid, Q, Vi, dst, wr2, nres)
+  ACS_G_SWITCH(d.G, XC_LIN)
 #undef XC_LIN
-  const size_t lds_schur = sizeof(double) * (size_t)d.chunk * K * 18 + sizeof(int) * (size_t)d.chunk * K;
-  hipLaunchKernelGGL(k_extcov_schur, dim3(nchunk), dim3(256), lds_schur, s, d, (const double*)Q, (const double*)Vi,
-                     (const int32_t*)dst, (const uint8_t*)mk, (const uint8_t*)cid, part);
+  hipLaunchKernelGGL(k_extcov_schur, dim3(nchunk), dim3(256), ext_schur_lds(d, 0), s, d, Q, Vi, dst, in.mask, in.camid,
+                     part);
   XcCamArgs ar{nchunk, anchored ? ACS_GAUGE_ANCHOR : ACS_GAUGE_FREE, anchored ? op.anchor_cam : 0,
                anchored ? op.scale_cam : 0, op.sigma_px * op.sigma_px};
-  hipLaunchKernelGGL(k_extcov_cams, dim3(1), dim3(256), extcov_cams_lds(NP), s, d, ar, (const double*)part,
-                     (const double*)dcam, (const int32_t*)dst, (const double*)wr2, (const int32_t*)nres, Ag, T1, T2,
-                     dcc, drep, bad);
+  hipLaunchKernelGGL(k_extcov_cams, dim3(1), dim3(256), extcov_cams_lds(NP), s, d, ar, part, in.cams, dst, wr2, nres, Ag,
+                     T1, T2, dcc, drep, bad);
   if (dcp) {
-#define XC_PTS(g)                                                                                                  \
-  hipLaunchKernelGGL((k_extcov_points<g>), dim3(blocks), dim3(256), sizeof(double) * nE, s, d, (const double*)dcc, \
-                     (const double*)Q, (const double*)Vi, (const int32_t*)dst, (const uint8_t*)mk,                  \
-                     (const uint8_t*)cid, ar.s2, (const acs_sba_ext_cov_report*)drep, dcp)
-    XC_G_SWITCH(G, XC_PTS)
+#define XC_PTS(g)                                                                                                   \
+  hipLaunchKernelGGL((k_extcov_points<g>), dim3(blocks), dim3(256), sizeof(double) * nE, s, d, dcc, Q, Vi, dst, in.mask, \
+                     in.camid, ar.s2, drep, dcp)
+    ACS_G_SWITCH(d.G, XC_PTS)
 #undef XC_PTS
   }
   ACS_HIP(ctx, hipGetLastError());

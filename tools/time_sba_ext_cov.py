@@ -9,7 +9,7 @@ untimed call that sizes the workspace. One run each (recorded, not a target). Th
 solve's time divided by the iterations its report gives. No oracle, no reference reads: it only
 times. The table goes to --out as JSON (one record per shape) and to stdout.
 
-    python tools/time_sba_ext_cov.py [--out profiles/r15/sba_ext_cov_time.json]
+    python tools/time_sba_ext_cov.py [--cov-calls 30] [--out profiles/r15/sba_ext_cov_time.json]
 """
 import argparse
 import ctypes as C
@@ -55,7 +55,7 @@ def _timed(dev, fn):
     return s.elapsed_time(e), out
 
 
-def time_case(ctx, dev, name, cams, uv, pi, ci, X0, max_iters):
+def time_case(ctx, dev, name, cams, uv, pi, ci, X0, max_iters, cov_calls=1):
     T = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dt)).to(dev)  # noqa: E731
     n, nc, m = len(X0), len(cams), len(pi)
     d_uv, d_pi, d_ci = T(uv, np.float64), T(pi, np.int32), T(ci, np.int32)
@@ -97,6 +97,10 @@ def time_case(ctx, dev, name, cams, uv, pi, ci, X0, max_iters):
                solve_status=srep.as_dict()['status_name'], lm_iteration_ms=round(solve_ms / iters, 5),
                cov_ms=round(cov_ms, 4), cov_over_lm_iteration=round(cov_ms / (solve_ms / iters), 3),
                alloc_events_in_timed_calls=_native.alloc_events() - before, cov_report=crep.as_dict())
+    if cov_calls > 1:  # one call is at the mercy of a single stall: the spread of repeats in one process
+        ts = sorted(cov(d_cams, d_pts) for _ in range(cov_calls))
+        rec['cov_ms_repeats'] = dict(calls=cov_calls, median=round(ts[len(ts) // 2], 4), min=round(ts[0], 4),
+                                     max=round(ts[-1], 4))
     print(json.dumps(rec), flush=True)
     return rec
 
@@ -105,6 +109,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=os.path.join('profiles', 'r15', 'sba_ext_cov_time.json'))
     ap.add_argument('--max-iters', type=int, default=40)
+    ap.add_argument('--cov-calls', type=int, default=1, help='further timed covariance calls (median, min, max)')
     a = ap.parse_args()
     device = int(os.environ.get('ACINOSET_DEVICE', 0))
     ctx = _native.Context(device)
@@ -118,7 +123,7 @@ def main():
                g['point_indices'], g['camera_indices'], g['points_3d']),
               ('16 cameras x 400 points',) + ring_problem(400, 16),
               ('board-sized: 6 cameras x 20,000 points',) + ring_problem(20000, 6)]
-    out = [time_case(ctx, dev, *s, a.max_iters) for s in shapes]
+    out = [time_case(ctx, dev, *s, a.max_iters, a.cov_calls) for s in shapes]
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, 'w') as f:
         json.dump(out, f, indent=1)
