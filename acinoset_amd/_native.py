@@ -52,6 +52,7 @@ SYMBOLS = (
     'acs_project_standard', 'acs_sba_lm_layout_flags',
     'acs_sba_points_covariance', 'acs_sba_points_dense_covariance',
     'acs_sba_ext_cov_default_opts', 'acs_sba_extrinsics_covariance',
+    'acs_sba_boards', 'acs_sba_boards_chunk',
 )
 
 
@@ -248,6 +249,9 @@ def _declare(lib):
                                            _P, _P, C.POINTER(Report), u32]),
         'acs_sba_extrinsics': (C.c_int, [_P, _P, i32, _P, _P, _P, i64, _P, i64, C.POINTER(SbaExtOpts), _P, _P,
                                          C.POINTER(SbaExtReport), u32]),
+        'acs_sba_boards': (C.c_int, [_P, _P, i32, _P, i32, _P, _P, i32, _P, C.POINTER(SbaExtOpts), _P, _P,
+                                     C.POINTER(SbaExtReport), u32]),
+        'acs_sba_boards_chunk': (i32, [i32]),
     }
     for name, (res, args) in sig.items():
         if not hasattr(lib, name):
@@ -283,6 +287,12 @@ def alloc_events():
     """acs_alloc_events: device / pinned-host allocations + frees the library has made in this
     process (no GPU needed)."""
     return int(load_library().acs_alloc_events())
+
+
+def sba_boards_chunk(n_cams):
+    """acs_sba_boards_chunk: boards per Schur block of acs_sba_boards for n_cams cameras (no GPU
+    needed)."""
+    return int(load_library().acs_sba_boards_chunk(int(n_cams)))
 
 
 def load_library():
@@ -600,6 +610,39 @@ class Context:
                                                _ptr(pts), len(pts), C.byref(opts), _ptr(rb), _ptr(ra),
                                                C.byref(rep), _std_flag(cams)), 'acs_sba_extrinsics')
         return cams, pts, rb, ra, rep.as_dict()
+
+    def sba_boards(self, cams, obj_pts, uv, mask, board_r, board_t, opts=None, residuals=True):
+        """acs_sba_boards: camera extrinsics and one rigid pose per board image. cams (C, 20) fisheye
+        records, obj_pts (nc, 3) board coordinates, uv (B, C, nc, 2), mask (B, C), board_r (B, 3, 3) and
+        board_t (B, 3) with X = R_b p + t_b. Returns (cams, board_r, board_t, res_before, res_after,
+        report); the residuals hold the seen views in (board, camera, corner, row) order."""
+        cams = _c64(cams).copy()
+        obj = _c64(obj_pts).reshape(-1, 3)
+        mask = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
+        n_b, n_c = mask.shape
+        uv = _c64(uv, (n_b, n_c, len(obj), 2))
+        poses = np.concatenate([_c64(board_r, (n_b, 9)), _c64(board_t, (n_b, 3))], 1)
+        n_res = 2 * len(obj) * int(mask.sum())
+        rb = np.empty(n_res) if residuals else None
+        ra = np.empty(n_res) if residuals else None
+        rep = SbaExtReport()
+        opts = opts or self.sba_ext_opts()
+        self.check(self.lib.acs_sba_boards(self.h, _ptr(cams), len(cams), _ptr(obj), len(obj), _ptr(uv), _ptr(mask),
+                                           n_b, _ptr(poses), C.byref(opts), _ptr(rb), _ptr(ra), C.byref(rep),
+                                           _std_flag(cams)), 'acs_sba_boards')
+        return cams, poses[:, :9].reshape(n_b, 3, 3).copy(), poses[:, 9:].copy(), rb, ra, rep.as_dict()
+
+    def sba_boards_dev(self, cams_p, n_cams, obj_p, n_corners, uv_p, mask_p, n_boards, poses_p, opts=None,
+                       resid_before_p=0, resid_after_p=0):
+        """acs_sba_boards on raw device addresses (ACS_DEVICE_PTRS): cameras and board poses (B, 12) are
+        refined in place; returns the report dict."""
+        rep = SbaExtReport()
+        opts = opts or self.sba_ext_opts()
+        v = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+        self.check(self.lib.acs_sba_boards(self.h, v(cams_p), n_cams, v(obj_p), n_corners, v(uv_p), v(mask_p), n_boards,
+                                           v(poses_p), C.byref(opts), v(resid_before_p), v(resid_after_p),
+                                           C.byref(rep), ACS_DEVICE_PTRS), 'acs_sba_boards')
+        return rep.as_dict()
 
     def sba_extrinsics_covariance(self, cams, uv, pt_idx, cam_idx, pts, f_scale=1.0, sigma_px=1.0, gauge='anchor',
                                   anchor=(0, 1), points=True):

@@ -25,25 +25,7 @@
 #include "mfma64.hpp"
 #include "sba_ext.hpp"
 
-// damping floor: the 7-DoF similarity gauge is left free (as in the reference), so the
-// reduced camera system is singular up to lambda; below ~1e-8 its gauge directions are
-// resolved by rounding alone. Spec shared with oracle/sba_ext.py (LAM_MIN).
-#define EXT_LAM_MIN 1e-7
-
-struct ExtState {
-  double F, F0, lam, gmax, dnorm, xnorm;
-  int cur, status, iters, nacc, relin, pad;
-  // rank round protocol (acs_sba_ext_dist_round): first round pending, a trial awaiting
-  // its decision, the speculative swap of the state for the next system
-  int first, pending, spec_on, save_cur;
-  double save_lam;
-};
 #define EXT_STATUS_SKIP 100  // a rejected round: no step, the system is re-formed only
-
-struct ExtOpts {
-  int max_iters;
-  double ftol, xtol, gtol;
-};
 
 template <int G>
 __global__ __launch_bounds__(256) void k_ext_linearize(ExtDims d, const ExtState* __restrict__ st,
@@ -289,22 +271,7 @@ __global__ void k_ext_cam(ExtDims d, const ExtState* __restrict__ st, const doub
   double* cn = camsbuf + ((cur ^ 1) * d.C + c) * ACS_CAM_STRIDE;
   for (int i = 0; i < 8; ++i) cn[i] = cm[i];
   const double w0 = dc[6 * c], w1 = dc[6 * c + 1], w2 = dc[6 * c + 2];
-  const double th = sqrt(w0 * w0 + w1 * w1 + w2 * w2);
-  double E[9];
-  if (th < 1e-300) {
-    for (int i = 0; i < 9; ++i) E[i] = (i % 4 == 0) ? 1.0 : 0.0;
-  } else {
-    const double k0 = w0 / th, k1 = w1 / th, k2 = w2 / th, cs = cos(th), sn = sin(th), oc = 1.0 - cs;
-    E[0] = cs + oc * k0 * k0;
-    E[1] = oc * k0 * k1 - sn * k2;
-    E[2] = oc * k0 * k2 + sn * k1;
-    E[3] = oc * k1 * k0 + sn * k2;
-    E[4] = cs + oc * k1 * k1;
-    E[5] = oc * k1 * k2 - sn * k0;
-    E[6] = oc * k2 * k0 - sn * k1;
-    E[7] = oc * k2 * k1 + sn * k0;
-    E[8] = cs + oc * k2 * k2;
-  }
+  EXT_EXP_SO3(E, w0, w1, w2)
   for (int i = 0; i < 3; ++i)
     for (int j = 0; j < 3; ++j)
       cn[8 + i * 3 + j] = E[i * 3] * cm[8 + j] + E[i * 3 + 1] * cm[8 + 3 + j] + E[i * 3 + 2] * cm[8 + 6 + j];
@@ -492,15 +459,31 @@ static size_t ext_solve_lds(int C) {
   return sizeof(double) * ((size_t)NP * (NP + 1) + NP + 512 + 256);
 }
 
+// the launches the rigid-board SBA (sba_boards.hip) shares with this file (declared in sba_ext.hpp)
+void ext_launch_solve(hipStream_t s, const ExtDims& d, ExtState* st, const double* sys, int nsys, const double* Vg,
+                      int n_gp, const double* slots, int n_slots, double* dc, double* Sg, int* bad) {
+  hipLaunchKernelGGL(k_ext_solve, dim3(1), dim3(256), ext_solve_lds(d.C), s, d, st, nsys, sys, Vg, n_gp, slots,
+                     n_slots, dc, Sg, bad);
+}
+
+void ext_launch_cam(hipStream_t s, const ExtDims& d, const ExtState* st, const double* dc, double* cams,
+                    double* camnorm) {
+  hipLaunchKernelGGL(k_ext_cam, dim3(1), dim3(64), 0, s, d, st, dc, cams, camnorm);
+}
+
+void ext_launch_lm(hipStream_t s, const ExtDims& d, ExtState* st, const ExtOpts& o, int init, const double* Fp,
+                   const double* normp, const double* camnorm) {
+  hipLaunchKernelGGL(k_ext_lm, dim3(1), dim3(256), 0, s, d, st, o, init, Fp, normp, camnorm);
+}
+
 // the camera step from the nsys partial systems at sys (the point-gradient maximum from n_gp
 // points of Vg and n_slots per-rank values), the point steps, the trial cameras
 static void ext_launch_step(hipStream_t s, const ExtDims& d, const ExtBuffers& b, const double* sys, int nsys,
                             int n_gp, const double* slots, int n_slots) {
-  hipLaunchKernelGGL(k_ext_solve, dim3(1), dim3(256), ext_solve_lds(d.C), s, d, b.st, nsys, sys, b.Vg, n_gp, slots,
-                     n_slots, b.dc, b.Sg, b.bad);
+  ext_launch_solve(s, d, b.st, sys, nsys, b.Vg, n_gp, slots, n_slots, b.dc, b.Sg, b.bad);
   hipLaunchKernelGGL(k_ext_back, dim3(acs_grid(d.n, 256)), dim3(256), 0, s, d, b.st, b.Q, b.Vg, b.mk, b.cid, b.dc, b.pts,
                      b.normp);
-  hipLaunchKernelGGL(k_ext_cam, dim3(1), dim3(64), 0, s, d, b.st, b.dc, b.cams, b.camnorm);
+  ext_launch_cam(s, d, b.st, b.dc, b.cams, b.camnorm);
 }
 
 // the robust cost per point: which = 0 at the current state, 1 at the trial
@@ -518,10 +501,10 @@ static void ext_enqueue(hipStream_t s, const ExtDims& d, const ExtOpts& o, const
   ext_launch_system(s, d, b);
   ext_launch_step(s, d, b, b.part, b.nchunk, d.n, nullptr, 0);
   ext_launch_cost(s, d, b, 1);
-  hipLaunchKernelGGL(k_ext_lm, dim3(1), dim3(256), 0, s, d, b.st, o, 0, b.Fp, b.normp, b.camnorm);
+  ext_launch_lm(s, d, b.st, o, 0, b.Fp, b.normp, b.camnorm);
 }
 
-static void ext_report(acs_sba_ext_report* report, const ExtState& hs, int nbad) {
+void ext_report(acs_sba_ext_report* report, const ExtState& hs, int nbad) {
   report->status = hs.status == 0 ? ACS_STATUS_MAXITER : hs.status;
   report->iters = hs.iters;
   report->n_accepted = hs.nacc;
@@ -580,7 +563,7 @@ int acs_sba_extrinsics(acs_ctx* ctx, double* cams, int32_t n_cams, const double*
   if ((rc = ext_start(ctx, d, b, in, op.lambda0, 0))) return rc;
   ExtOpts o{op.max_iters, op.ftol, op.xtol, op.gtol};
   ext_launch_cost(s, d, b, 0);
-  hipLaunchKernelGGL(k_ext_lm, dim3(1), dim3(256), 0, s, d, b.st, o, 1, b.Fp, b.normp, b.camnorm);
+  ext_launch_lm(s, d, b.st, o, 1, b.Fp, b.normp, b.camnorm);
   ACS_HIP(ctx, hipGetLastError());
   const int chunk = 4;
   hipGraph_t graph = nullptr;

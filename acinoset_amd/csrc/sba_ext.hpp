@@ -1,6 +1,8 @@
 // sba_ext.hpp — what the points + extrinsics SBA (sba_ext.hip) and its covariance
 // (sba_ext_cov.hip) share: the problem's dimensions, the slot record, an observation's blocks
-// (ext_obs_blocks) and the Schur partials (ext_schur_stage, ext_schur_entry).
+// (ext_obs_blocks) and the Schur partials (ext_schur_stage, ext_schur_entry); and what the
+// rigid-board SBA (sba_boards.hip) takes from the solver: the LM state and options, the launches
+// of k_ext_solve / k_ext_cam / k_ext_lm and the exponential map (EXT_EXP_SO3).
 #pragma once
 
 #include <algorithm>
@@ -10,6 +12,7 @@
 #define EXT_MAXC 16
 #define EXT_CHUNK 64
 #define EXT_MAXK 64  // observations of one point: one 64-lane group, one slot per lane
+#define BRD_MAXNC 256  // corners of a rigid board (sba_boards.hip): four rounds of one wave
 
 // The slot record, EXT_Q doubles per observation slot: U (21 packed upper), W = J_cam^T J_pt (6 x 3)
 // and, in the solver's record only (GC = true), the camera gradient g_c (6) behind them.
@@ -38,6 +41,60 @@ static inline int ext_nchunk(const ExtDims& d) { return (d.n + d.chunk - 1) / d.
 static inline size_t ext_schur_lds(const ExtDims& d, int per_point) {
   return sizeof(double) * ((size_t)d.chunk * d.K * 18 + d.chunk * per_point) + sizeof(int) * (size_t)d.chunk * d.K;
 }
+
+// damping floor: the gauge is left free (as in the reference: the 7-DoF similarity of the free
+// points, the 6-DoF rigid motion of the rigid boards), so the reduced camera system is singular
+// up to lambda; below ~1e-8 its gauge directions are resolved by rounding alone. Spec shared
+// with oracle/sba_ext.py (LAM_MIN).
+#define EXT_LAM_MIN 1e-7
+
+struct ExtState {
+  double F, F0, lam, gmax, dnorm, xnorm;
+  int cur, status, iters, nacc, relin, pad;
+  // rank round protocol (acs_sba_ext_dist_round): first round pending, a trial awaiting
+  // its decision, the speculative swap of the state for the next system
+  int first, pending, spec_on, save_cur;
+  double save_lam;
+};
+
+struct ExtOpts {
+  int max_iters;
+  double ftol, xtol, gtol;
+};
+
+// The launches of sba_ext.hip that the rigid-board SBA (sba_boards.hip) takes as they are: the
+// camera step from nsys partial systems at sys (k_ext_solve; the gradient maximum of the other
+// side from n_gp points of Vg and n_slots values), the trial cameras (k_ext_cam), and the first
+// cost (init) or the LM decision over d.n cost and norm entries (k_ext_lm).
+void ext_launch_solve(hipStream_t s, const ExtDims& d, ExtState* st, const double* sys, int nsys, const double* Vg,
+                      int n_gp, const double* slots, int n_slots, double* dc, double* Sg, int* bad);
+void ext_launch_cam(hipStream_t s, const ExtDims& d, const ExtState* st, const double* dc, double* cams,
+                    double* camnorm);
+void ext_launch_lm(hipStream_t s, const ExtDims& d, ExtState* st, const ExtOpts& o, int init, const double* Fp,
+                   const double* normp, const double* camnorm);
+void ext_report(acs_sba_ext_report* report, const ExtState& hs, int nbad);
+
+// double E[9] = exp([w]x), row-major (Rodrigues; the identity below |w| = 1e-300), declared in the
+// caller's scope. The text of k_ext_cam's update, shared with k_brd_pose (sba_boards.hip); a macro,
+// not a function: as an inlined function the same statements give k_ext_cam other registers.
+#define EXT_EXP_SO3(E, w0, w1, w2)                                                                             \
+  const double E##_th = sqrt((w0) * (w0) + (w1) * (w1) + (w2) * (w2));                                         \
+  double E[9];                                                                                                 \
+  if (E##_th < 1e-300) {                                                                                       \
+    for (int i = 0; i < 9; ++i) E[i] = (i % 4 == 0) ? 1.0 : 0.0;                                               \
+  } else {                                                                                                     \
+    const double k0 = (w0) / E##_th, k1 = (w1) / E##_th, k2 = (w2) / E##_th, cs = cos(E##_th), sn = sin(E##_th), \
+                 oc = 1.0 - cs;                                                                                \
+    E[0] = cs + oc * k0 * k0;                                                                                  \
+    E[1] = oc * k0 * k1 - sn * k2;                                                                             \
+    E[2] = oc * k0 * k2 + sn * k1;                                                                             \
+    E[3] = oc * k1 * k0 + sn * k2;                                                                             \
+    E[4] = cs + oc * k1 * k1;                                                                                  \
+    E[5] = oc * k1 * k2 - sn * k0;                                                                             \
+    E[6] = oc * k2 * k0 - sn * k1;                                                                             \
+    E[7] = oc * k2 * k1 + sn * k0;                                                                             \
+    E[8] = cs + oc * k2 * k2;                                                                                  \
+  }
 
 __device__ __forceinline__ int upk(int i, int j) {  // packed upper-triangular index, 6x6
   if (i > j) {

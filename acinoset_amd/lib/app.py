@@ -13,7 +13,7 @@ import numpy as np
 
 from . import misc, utils
 from .calib import project_points, project_points_fisheye, triangulate_points, triangulate_points_fisheye
-from .sba import _sba_board_points, _sba_points
+from .sba import _sba_board_points, _sba_board_poses, _sba_points
 
 
 def sba_points_standard(scene_fpath, points_2d_df, covariance=False, sigma_px=1.0):
@@ -32,6 +32,13 @@ def sba_board_points_fisheye(scene_fpath, points_fpaths, out_fpath, manual_point
     return _sba_board_points(scene_fpath, points_fpaths, manual_points_fpath, out_fpath, triangulate_points_fisheye,
                              project_points_fisheye, camera_indices, manual_points_only, covariance=covariance,
                              sigma_px=sigma_px)
+
+
+def sba_board_poses_fisheye(scene_fpath, points_fpaths, out_fpath, camera_indices=None):
+    """Extrinsics refined with one rigid pose per board image and the known square length
+    (`_sba_board_poses`): the scene JSON at out_fpath and `<out_fpath stem>_boards.json` beside it.
+    Hand-labelled manual points are not part of this solve."""
+    return _sba_board_poses(scene_fpath, points_fpaths, out_fpath, camera_indices)
 
 
 def _gaze_targets(head_pos, nose_pos, r_eye_pos, r=3.0):

@@ -421,3 +421,110 @@ def save_pose_covariance(fpath, res, r_arr, t_arr, sigma_px):
                          for c in range(len(blocks))])
     with open(fpath, 'w') as f:
         json.dump(data, f, indent=2)
+
+
+# ---- rigid-board bundle adjustment: one pose per board image (acs_sba_boards) -------------
+
+def board_poses_from_points(obj_pts, pts_3d):
+    """Rigid fit (Kabsch, det > 0) of the board model to triangulated corners: obj_pts (nc, 3) board
+    coordinates, pts_3d (B, nc, 3) or (nc, 3) world points. Returns (board_r (B, 3, 3), board_t (B, 3))
+    with X = R p + t in the least-squares sense. Host numpy: a one-off initialisation."""
+    p = np.asarray(obj_pts, np.float64).reshape(-1, 3)
+    X = np.asarray(pts_3d, np.float64).reshape(-1, len(p), 3)
+    pm = p.mean(0)
+    r_out, t_out = np.empty((len(X), 3, 3)), np.empty((len(X), 3))
+    for b, Xb in enumerate(X):
+        xm = Xb.mean(0)
+        U, _, Vt = np.linalg.svd((Xb - xm).T @ (p - pm))
+        R = U @ np.diag([1.0, 1.0, np.sign(np.linalg.det(U @ Vt)) or 1.0]) @ Vt
+        r_out[b] = R
+        t_out[b] = xm - R @ pm
+    return r_out, t_out
+
+
+def prepare_calib_boards_for_bundle_adjustment(img_pts_arr, fnames_arr, board_shape, square_len, k_arr, d_arr, r_arr,
+                                               t_arr):
+    """The rigid-board form of prepare_calib_board_data_for_bundle_adjustment, with its image-name
+    rule (sorted names, seen by at least two cameras): one board per such image. Returns
+    (uv (B, C, nc, 2) float64, zero where unseen; mask (B, C) uint8; obj_pts (nc, 3); board_r (B, 3, 3);
+    board_t (B, 3); names), the initial poses fitted (board_poses_from_points) to the corners
+    triangulated from each board's first two cameras, all boards in one GPU batch."""
+    from .utils import create_board_object_pts
+    n_cam = len(img_pts_arr)
+    lists = [list(f) for f in fnames_arr]
+    seen = {}
+    for fnames in lists:
+        for fn in set(fnames):
+            seen[fn] = seen.get(fn, 0) + 1
+    names = sorted(k for k, v in seen.items() if v >= 2)
+    nc = board_shape[0] * board_shape[1]
+    obj = np.asarray(create_board_object_pts(board_shape, square_len), np.float64)
+    uv = np.zeros((len(names), n_cam, nc, 2))
+    mask = np.zeros((len(names), n_cam), np.uint8)
+    jobs = []
+    for b, fn in enumerate(names):
+        cams = [c for c in range(n_cam) if fn in lists[c]]
+        for c in cams:
+            uv[b, c] = np.asarray(img_pts_arr[c][lists[c].index(fn)], np.float64).reshape(nc, 2)
+            mask[b, c] = 1
+        jobs.append((uv[b, cams[0]], uv[b, cams[1]], cams[0], cams[1]))
+    pts = _triangulate_batch(jobs, k_arr, d_arr, r_arr, t_arr, None)
+    if not jobs:
+        return uv, mask, obj, np.zeros((0, 3, 3)), np.zeros((0, 3)), names
+    board_r, board_t = board_poses_from_points(obj, np.stack(pts))
+    return uv, mask, obj, board_r, board_t, names
+
+
+def bundle_adjust_boards_and_extrinsics(uv, mask, obj_pts, board_r, board_t, k_arr, d_arr, r_arr, t_arr, f_scale=1.0,
+                                        **opts):
+    """acs_sba_boards: every camera's rotation and translation (intrinsics fixed, fisheye model) and one
+    rigid pose per board image refined together on the Cauchy objective of
+    bundle_adjust_points_and_extrinsics. The known board geometry fixes the metric scale. uv
+    (B, C, nc, 2), mask (B, C), obj_pts (nc, 3), board poses X = board_r p + board_t. Returns (board_r
+    (B, 3, 3), board_t (B, 3), r_arr (C, 3, 3), t_arr (C, 3, 1), {'before', 'after', 'report'}); the
+    residuals hold the seen views in (board, camera, corner, row) order. opts: max_iters, ftol, xtol,
+    gtol, lambda0."""
+    ctx = _native.default_context()
+    n = len(k_arr)
+    o = ctx.sba_ext_opts(f_scale=float(f_scale), **opts)
+    t0 = time()
+    cams, br, bt, rb, ra, rep = ctx.sba_boards(_cams(k_arr, d_arr, r_arr, t_arr), obj_pts, uv, mask, board_r, board_t, o)
+    t1 = time()
+    print(f'GPU SBA (boards + extrinsics): {len(br)} boards of {len(np.asarray(obj_pts).reshape(-1, 3))} corners, '
+          f'{int(np.count_nonzero(mask))} views, {n} cameras, {rep["iters"]} iterations, cost '
+          f'{rep["cost_before"]:.6e} -> {rep["cost_after"]:.6e} ({rep["status_name"]})')
+    print(f'\nOptimization took {t1 - t0:.2f} seconds')
+    r_out = cams[:, 8:17].reshape(n, 3, 3).copy()
+    t_out = cams[:, 17:20].reshape(n, 3, 1).copy()
+    return br, bt, r_out, t_out, dict(before=rb, after=ra, report=rep)
+
+
+def _sba_board_poses(scene_fpath, points_fpaths, out_fpath, camera_indices=None):
+    """Board corners -> rigid-board SBA (bundle_adjust_boards_and_extrinsics) -> refined scene JSON at
+    out_fpath and `<out_fpath stem>_boards.json` beside it: per board image its name, pose (r, t) and
+    view count, and the report. The square length is the points files'. Returns the residual dict."""
+    img_pts_arr, fnames_arr, board_shape, square_len = [], [], None, None
+    if camera_indices is None:
+        camera_indices = range(len(points_fpaths))
+    for i in camera_indices:
+        points, fnames, board_shape, square_len, *_ = load_points(points_fpaths[i])
+        img_pts_arr.append(points)
+        fnames_arr.append(fnames)
+    k_arr, d_arr, r_arr, t_arr, cam_res = load_scene(scene_fpath)
+    assert len(k_arr) == len(img_pts_arr)
+    print('bundle_adjust_boards_and_extrinsics')
+    uv, mask, obj, br, bt, names = prepare_calib_boards_for_bundle_adjustment(img_pts_arr, fnames_arr, board_shape,
+                                                                              square_len, k_arr, d_arr, r_arr, t_arr)
+    br, bt, r_arr, t_arr, res = bundle_adjust_boards_and_extrinsics(uv, mask, obj, br, bt, k_arr, d_arr, r_arr, t_arr)
+    print(f"\nBefore: mean: {np.mean(res['before'])}, std: {np.std(res['before'])}")
+    print(f"After: mean: {np.mean(res['after'])}, std: {np.std(res['after'])}\n")
+    save_scene(out_fpath, k_arr, d_arr, r_arr, t_arr, cam_res)
+    rep = {k: v for k, v in res['report'].items() if isinstance(v, (int, float, str))}
+    data = dict(board_shape=list(board_shape), board_square_len=float(square_len),
+                parameters='per board X = r p + t: board coordinates to world coordinates (m)',
+                boards=[dict(name=fn, r=br[b].tolist(), t=bt[b].tolist(), n_views=int(mask[b].sum()))
+                        for b, fn in enumerate(names)], report=rep)
+    with open(os.path.splitext(out_fpath)[0] + '_boards.json', 'w') as f:
+        json.dump(data, f, indent=2)
+    res.update(board_r=br, board_t=bt, names=names, mask=mask, uv=uv, obj_pts=obj)
+    return res

@@ -395,6 +395,40 @@ int acs_sba_extrinsics(acs_ctx* ctx, double* cams, int32_t n_cams, const double*
                        int64_t n_pts, const acs_sba_ext_opts* opts, double* resid_before,
                        double* resid_after, acs_sba_ext_report* report, uint32_t flags);
 
+/* ---- bundle adjustment of extrinsics AND rigid calibration-board poses ------------------
+ * One rigid pose per board image instead of one free 3-D point per corner: the known board
+ * geometry fixes the metric scale, and the gauge is the 6-DoF rigid motion only.
+ *   cameras c = 0..n_cams-1: fisheye records (ACS_CAM_STRIDE), intrinsics kept, 1..16
+ *   boards b = 0..n_boards-1: pose (R_b, t_b) from board to world coordinates, as 12 doubles
+ *     (R row-major, then t); in/out
+ *   obj_pts (n_corners, 3): the target's points p_j in board coordinates (any rigid target,
+ *     e.g. create_board_object_pts), 3 <= n_corners <= 256
+ *   world point X_bj = R_b p_j + t_b
+ *   uv (n_boards, n_cams, n_corners, 2) pixels and mask (n_boards, n_cams) uint8: a camera sees
+ *     a board image with all its corners or not at all
+ *   residual r = project(R_c X_bj + t_c) - uv; cost F = 1/2 f^2 sum log1p(r^2 / f^2); weights
+ *     w = 1 / (1 + z), wh = max((1 - z) w^2, 0.1 w), z = r^2 / f^2 (those of acs_sba_extrinsics)
+ *   left perturbations R <- exp([dw]x) R, t <- t + dt for cameras and boards;
+ *     J_cam = J_Y [-[R_c X]x | I], J_pt = J_Y R_c, J_brd = J_pt [-[R_b p_j]x | I]
+ *   per seen view: U_bc = sum wh J_cam^T J_cam, W_bc = sum wh J_cam^T J_brd (6 x 6), g_c;
+ *     per board: V_b = sum wh J_brd^T J_brd (6 x 6), g_b
+ *   LM of acs_sba_extrinsics with the boards eliminated: M_b = (V_b + lam diag V_b + 1e-300 I)^-1,
+ *     S = sum U + lam D - sum W M W^T, b = -g_c + sum W M g_b, db = -M_b (g_b + sum W^T dc);
+ *     accept iff the cost falls (lam /= 10, floor 1e-7), else lam *= 10; stops, options and
+ *     report as acs_sba_extrinsics (|d|^2 = sum dc^2 + sum db^2, |x|^2 = sum |t_c|^2 + sum |t_b|^2)
+ *   a board whose damped V_b is not positive definite (no view, a NaN, a pivot not > 0) takes
+ *     no step in that iteration; a board with one view is legal. The rigid gauge is left free.
+ * resid_before / resid_after (either may be NULL): the seen views in (board, camera, corner, row)
+ * order, 2 n_corners doubles per seen view. Host pointers, or ACS_DEVICE_PTRS for every array.
+ * ACS_E_INVALID before anything is staged: f_scale <= 0, n_cams outside 1..16, n_corners outside
+ * 3..256, n_boards < 1, ACS_CAMS_STANDARD.
+ * acs_sba_boards_chunk: boards per block of the Schur complement for n_cams cameras (test hook). */
+int acs_sba_boards(acs_ctx* ctx, double* cams, int32_t n_cams, const double* obj_pts,
+                   int32_t n_corners, const double* uv, const uint8_t* mask, int32_t n_boards,
+                   double* board_poses, const acs_sba_ext_opts* opts, double* resid_before,
+                   double* resid_after, acs_sba_ext_report* report, uint32_t flags);
+int32_t acs_sba_boards_chunk(int32_t n_cams);
+
 /* ---- camera-pose and joint point covariances of the points + extrinsics SBA -----------
  * Evaluated at the cameras (fisheye records, n_cams <= 16) and points passed in; nothing is
  * solved. Observation list as acs_sba_extrinsics.
