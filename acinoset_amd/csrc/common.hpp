@@ -4,10 +4,12 @@
 
 #include <hip/hip_runtime.h>
 
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -108,6 +110,15 @@ int acs_stage_out(acs_ctx* ctx, void* dst, const void* dev, size_t bytes, uint32
 void* acs_out_buf(acs_ctx* ctx, int slot, void* dst, size_t bytes, uint32_t flags);
 
 static inline int acs_grid(int64_t n, int block) { return (int)((n + block - 1) / block); }
+
+// Integer tuning knob from the environment: def when unset, else its value clamped to [lo, hi].
+// A caller keeps the result in a function-local static, so a knob is read once per process.
+// The value is read with atoi, so an on/off knob (def 0, tested == 1) is on at "1" and off at "10".
+static inline int acs_env_int(const char* name, int def, int lo = INT_MIN, int hi = INT_MAX) {
+  const char* e = std::getenv(name);
+  const int v = e ? std::atoi(e) : def;
+  return v < lo ? lo : (v > hi ? hi : v);
+}
 
 // An observation list (any order) on the device and its per-point slot tensor (n_pts, K): uvp, mask,
 // camid, deterministic (stable radix sort by point id); K = max obs/pt.

@@ -2462,16 +2462,10 @@ int acs_ekf_enqueue(acs_ctx* ctx, int n_ints, int n_reals, const int* hdr, int n
                                           (size_t)n_cams * ACS_CAM_STRIDE + n_reals + (n_ints + 1) / 2 + 1);
   const size_t lds_w1 = sizeof(double) * ekf_w1_lds(d);
   // ACS_EKF_WG=1 keeps the 8-wave kernel for every model (A/B measurements, tools/ekf_drift.py)
-  static const bool force_wg = [] {
-    const char* e = std::getenv("ACS_EKF_WG");
-    return e && e[0] == '1';
-  }();
+  static const bool force_wg = acs_env_int("ACS_EKF_WG", 0) == 1;
   const bool w1 = P == EKF_W1_P && lds_w1 <= 64 * 1024 && !force_wg;
   // ACS_EKF_W1_WAVES: waves per sequence of the small-state filter (4 by default; 1 for A/B)
-  static const int w1_waves = [] {
-    const char* e = std::getenv("ACS_EKF_W1_WAVES");
-    return e && e[0] == '1' ? 1 : 4;
-  }();
+  static const int w1_waves = acs_env_int("ACS_EKF_W1_WAVES", 4) == 1 ? 1 : 4;
   ACS_CHECK(ctx, w1 || lds_f <= 160 * 1024, "ekf: P = %d needs %zu bytes of LDS", P, lds_f);
   ACS_CHECK(ctx, ref_numerics >= 0 && ref_numerics <= ACS_EKF_ANALYTIC_H, "ekf: numerics mode %d", ref_numerics);
   // analytic H: the FkShared of one FK lives in the batched-FK region of the LDS union
@@ -2517,10 +2511,7 @@ int acs_ekf_enqueue(acs_ctx* ctx, int n_ints, int n_reals, const int* hdr, int n
   // shares a CU, tools/probe/lds_occ_probe.hip: the 72 KB one-gain form ran one gain per CU)
   // one gain per workgroup, two workgroups per CU: 4.09 ms for the bench's 64 x 499 gains;
   // two gains per 768-thread workgroup (lockstep barriers) 4.31 ms (ACS_EKF_GAIN_GP=2, A/B)
-  static const int gp = [] {
-    const char* e = std::getenv("ACS_EKF_GAIN_GP");
-    return e && std::atoi(e) == 2 ? 2 : 1;
-  }();
+  static const int gp = acs_env_int("ACS_EKF_GAIN_GP", 1) == 2 ? 2 : 1;
 #define EKF_GAIN_T(NB)                                                                                          \
   if (gp == 1)                                                                                                  \
     hipLaunchKernelGGL((k_ekf_gain_t<NB, 1>), dim3(ng), dim3(64 * NB), 0, s, d, (const double*)dPe, dPp, dflag, \

@@ -1378,24 +1378,6 @@ static size_t asm_build_lds_bytes(const FteDims& d, bool cmp) {
   return sizeof(double) * 3 * (size_t)((cmp ? RowCmp::size(d.P) : 4 * d.P * d.P) + d.P + d.P * d.Cg);
 }
 
-static void cr_launch_build(const FteDims& d, hipStream_t s, int nblk, const FteState* st, const double* Ab,
-                            const double* gb, const double* Bt, double* Dc, double* Ec, double* GBc, int b0,
-                            int end_l, int end_r, const double* Adiag) {
-  if (nblk <= 0) return;
-#define CR_BUILD(nb)                                                                                          \
-  hipLaunchKernelGGL((k_cr_build<nb>), dim3(nblk), dim3(1024), 0, s, d, st, Ab, gb, Bt, Dc, Ec, GBc, b0, end_l, \
-                     end_r, Adiag)
-  switch (d.BP >> 4) {
-    case 1: CR_BUILD(1); break;
-    case 2: CR_BUILD(2); break;
-    case 3: CR_BUILD(3); break;
-    case 4: CR_BUILD(4); break;
-    case 5: CR_BUILD(5); break;
-    default: CR_BUILD(6); break;
-  }
-#undef CR_BUILD
-}
-
 // Fixed-order partial sums feeding the tau border (parallel over chunks, summed in chunk
 // order by k_cr_top): per-frame tau blocks of the normal matrix / gradient, and the tau
 // Schur contributions of every eliminated super-block.
@@ -2958,859 +2940,14 @@ __global__ void k_fte_state_reset(FteState* __restrict__ st, double lam0) {
   *st = z;
 }
 
-struct FteBuffers {
-  int* I;
-  double *Rl, *cams, *meas, *w, *qinv, *X, *tau;
-  double *Hloc, *gloc, *Floc, *Tc, *Ab, *gb, *Bt, *gmaxp, *Dc, *Ec, *GBc, *Wc, *Tau, *dcv, *dtau, *normp, *Fm, *Fq, *part;
-  double* Adiag;
-  double *Ec2, *dL, *dR;  // second coupling buffer (levels alternate), pending Schur terms
-  // frame-window ranks with per-frame delays: rows' gradients before the delay elimination,
-  // per-row max |delay gradient| of the frame the row starts, per-block delay step / state norms
-  double *graw, *gmaxt, *normt;
-  int* bad;
-  int* bk;                    // k_cr_back_all: ticket counter, partials counter
-  unsigned long long* gdcv;   // k_cr_back_all: the step rows, then dtau, as {stamp, word} granules
-  FteState* st;
-};
+#include "fte_host.hpp"
+#include "fte_dist.hpp"
+// acs_fte_covariance: selected inversion of the undamped normal matrix (its own kernels)
+#include "fte_cov.hpp"
 
-// k_fte_linearize over frames [k0, k0 + nk) (spec: at the trial state, with the model terms in Fq)
-static void fte_launch_lin(const FteDims& d, hipStream_t s, const FteBuffers& b, int force, int k0, int nk, int spec,
-                           double* Fq, const double* qinv) {
-  const LinKernel kf = lin_kernel(nk);
-  const size_t lds = lin_lds_bytes(d);
-  hipLaunchKernelGGL(kf, dim3(nk), dim3(256), lds, s, d, b.I, b.Rl, b.cams, b.meas, b.w, b.X, b.tau,
-                     b.st, force, k0, b.Hloc, b.gloc, b.Floc, spec, Fq, qinv, b.Tc);
-}
-
-struct FteSetup {
-  FteState* snap = nullptr;  // pinned host slots the LM kernel writes its state into
-  int n_cu = 256;            // the context's device (k_cr_assemble_build's instance: cr_asm_threads)
-  FteDims d;
-  FteBuffers b;
-};
-
-// The sizes that choose the solve's kernels and grids: the 3-frame super-blocks (nblk of BP
-// rows), the tau border (Cg constant delays + the gradient column, GR wide) and the
-// cyclic-reduction depth
-static void fte_shape(FteDims& d, int N, int P, int n_cams, int sd, int sd_mode) {
-  d.N = N;
-  d.M = N + 2;
-  d.P = P;
-  d.C = n_cams;
-  d.var = sd && sd_mode == 1;
-  d.Ct = sd ? n_cams : 0;
-  d.Cg = sd && !d.var ? n_cams : 0;
-  d.NT = d.var ? N * n_cams : n_cams;
-  d.NZ = P + 6 + d.Ct;
-  d.nblk = (d.M + 2) / 3;
-  d.BP = ((3 * P + 15) / 16) * 16;
-  d.GR = ((d.Cg + 1 + 15) / 16) * 16;
-  d.nlev = 0;
-  for (int s = 1; s < d.nblk; s <<= 1) d.nlev++;
-}
-
-// Dimensions, device buffers and initial state of one FTE problem. With `owned` == NULL
-// the buffers live in the context workspace (acs_fte_solve / acs_fte_eval); otherwise one
-// hipMalloc block is allocated for them and returned in *owned (the distributed handles,
-// several of which may share a context).
-static int fte_setup(acs_ctx* ctx, FteSetup& S, const int32_t* skel_ints, int64_t n_ints, const double* skel_reals,
-                     int64_t n_reals, const double* cams, int32_t n_cams, const double* meas, const double* w,
-                     int32_t N, int32_t sd, double Ts, const double* qinv, int32_t sd_mode, int32_t intermode,
-                     const double* X, const double* tau, double la, double lb, double lc, uint32_t flags,
-                     void** owned = nullptr) {
-  int hdr[FK_HDR];
-  if (flags & ACS_DEVICE_PTRS)
-    ACS_HIP(ctx, hipMemcpy(hdr, skel_ints, sizeof(hdr), hipMemcpyDeviceToHost));
-  else
-    std::memcpy(hdr, skel_ints, sizeof(hdr));
-  const int Jn = hdr[0], K = hdr[1], P = hdr[2], L = hdr[3];
-  ACS_CHECK(ctx, Jn > 0 && Jn <= FK_MAXJ && K <= FK_MAXN && P >= 3 && P <= FK_MAXP && L >= 1 && L <= K,
-            "fte: skeleton table out of range");
-  ACS_CHECK(ctx, n_ints == FK_HDR + 9 * Jn + 4 * K + L + 4 * P + K * P && n_reals == 3 * K, "fte: blob sizes");
-  ACS_CHECK(ctx, N >= 2 && n_cams >= 1 && n_cams <= FTE_MAXC && Ts > 0, "fte: N=%d C=%d Ts=%g", N, n_cams, Ts);
-  ACS_CHECK(ctx, intermode >= 0 && intermode <= 2 && (sd ? intermode >= 1 : intermode == 0),
-            "fte: shutter_delay=%d needs intermode %s (got %d), as src/core/fte.py:44-48", sd,
-            sd ? "vel/acc" : "pos", intermode);
-  ACS_CHECK(ctx, sd_mode == 0 || sd_mode == 1, "fte: shutter_delay_mode %d (0 const, 1 variable)", sd_mode);
-  S.n_cu = ctx->n_cu;
-  FteDims& d = S.d;
-  fte_shape(d, N, P, n_cams, sd, sd_mode);
-  d.L = L;
-  d.nint = (int)n_ints;
-  d.nreal = (int)n_reals;
-  d.pad_ = 0;
-  ACS_CHECK(ctx, d.NZ <= FTE_NZP, "fte: P + 6 + C = %d exceeds %d", d.NZ, FTE_NZP);
-  d.im = intermode;
-  d.Ts = Ts;
-  d.la = la;
-  d.lb = lb;
-  d.lc = lc;
-  ACS_CHECK(ctx, d.BP <= CR_MAXBP, "fte: 3P = %d exceeds %d", 3 * P, CR_MAXBP);
-  const int M = d.M, C = d.C, BP = d.BP, GR = d.GR, n = d.nblk;
-  FteBuffers& b = S.b;
-  size_t off = 0;
-  auto take = [&](size_t cnt) {
-    size_t o = off;
-    off += ((cnt * sizeof(double) + 255) / 256) * 256 / sizeof(double);
-    return o;
-  };
-  const size_t Cg1 = d.Cg ? d.Cg : 1;
-  // the per-frame linearisation is double-buffered: the speculative linearisation of the
-  // trial state (k_fte_linearize spec = 1) writes copy cur ^ 1 (single-GPU and frame-window)
-  const size_t nlin = 2;
-  const size_t oX = take((size_t)2 * M * P), oT = take(2 * (size_t)d.NT), oAd = take((size_t)M * P),
-               oH = take(nlin * N * FTE_NZP * FTE_NZP), og = take(nlin * N * FTE_NZP), oF = take(nlin * N), oAb = take((size_t)M * 4 * P * P),
-               ogb = take((size_t)M * P), oBt = take((size_t)M * P * Cg1), ogm = take(M),
-               oD = take((size_t)n * BP * BP), oE = take((size_t)n * BP * BP), oG = take((size_t)n * BP * GR),
-               oW = take((size_t)n * BP * (2 * BP + GR)), oTau = take((size_t)n * GR * GR),
-               oE2 = take((size_t)n * BP * BP), odL = take((size_t)n * BP * (BP + GR)),
-               odR = take((size_t)n * BP * (BP + GR)),
-               odc = take((size_t)n * BP), odt = take(GR), opart = take((size_t)CR_NCHUNK * (32 * 32 + 32 + 32 * 32 + 1)),
-               onp = take(2 * (size_t)n), oTc = take(nlin * N * std::max(tc_stride(d.Cg), 1)), oFm = take(N), oFq = take(N), ost = take(16), oint = take(8),
-               ogr = take((size_t)M * P), ogt = take(M), ont = take(2 * (size_t)n),
-               obk = take((size_t)n / 2 + 2), ogd = take((size_t)n * BP * 2 + 64);
-  // staged inputs (owned mode only)
-  const size_t oI = take((n_ints + 1) / 2 + 1), oR = take(n_reals), oC = take((size_t)ACS_CAM_STRIDE * C),
-               oMe = take((size_t)N * C * L * 2), oWt = take((size_t)N * C * L), oQ = take(P);
-  double* arena;
-  const size_t inputs_from = oI;
-  hipStream_t s = ctx->stream;
-  const hipMemcpyKind kin = (flags & ACS_DEVICE_PTRS) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  int rc;
-  if (owned) {
-    void* p = nullptr;
-    ACS_HIP(ctx, acs_dev_malloc(&p, off * sizeof(double)));
-    *owned = p;
-    arena = (double*)p;
-    b.I = (int*)(arena + oI);
-    b.Rl = arena + oR;
-    b.cams = arena + oC;
-    b.meas = arena + oMe;
-    b.w = arena + oWt;
-    b.qinv = arena + oQ;
-    ACS_HIP(ctx, hipMemcpyAsync(b.I, skel_ints, sizeof(int32_t) * n_ints, kin, s));
-    ACS_HIP(ctx, hipMemcpyAsync(b.Rl, skel_reals, sizeof(double) * n_reals, kin, s));
-    ACS_HIP(ctx, hipMemcpyAsync(b.cams, cams, sizeof(double) * ACS_CAM_STRIDE * C, kin, s));
-    ACS_HIP(ctx, hipMemcpyAsync(b.meas, meas, sizeof(double) * (size_t)N * C * L * 2, kin, s));
-    ACS_HIP(ctx, hipMemcpyAsync(b.w, w, sizeof(double) * (size_t)N * C * L, kin, s));
-    ACS_HIP(ctx, hipMemcpyAsync(b.qinv, qinv, sizeof(double) * P, kin, s));
-  } else {
-    void* p;
-    if ((rc = acs_stage_in(ctx, WS_FTE0, skel_ints, sizeof(int32_t) * n_ints, flags, &p))) return rc;
-    b.I = (int*)p;
-    if ((rc = acs_stage_in(ctx, WS_FTE1, skel_reals, sizeof(double) * n_reals, flags, &p))) return rc;
-    b.Rl = (double*)p;
-    if ((rc = acs_stage_in(ctx, WS_CAMS, cams, sizeof(double) * ACS_CAM_STRIDE * C, flags, &p))) return rc;
-    b.cams = (double*)p;
-    if ((rc = acs_stage_in(ctx, WS_FTE2, meas, sizeof(double) * (size_t)N * C * L * 2, flags, &p))) return rc;
-    b.meas = (double*)p;
-    if ((rc = acs_stage_in(ctx, WS_FTE3, w, sizeof(double) * (size_t)N * C * L, flags, &p))) return rc;
-    b.w = (double*)p;
-    if ((rc = acs_stage_in(ctx, WS_FTE4, qinv, sizeof(double) * P, flags, &p))) return rc;
-    b.qinv = (double*)p;
-    arena = (double*)acs_ws(ctx, WS_FTE5, inputs_from * sizeof(double));
-    if (!arena) return ACS_E_NOMEM;
-  }
-  b.X = arena + oX;
-  b.tau = arena + oT;
-  b.Adiag = arena + oAd;
-  b.Hloc = arena + oH;
-  b.gloc = arena + og;
-  b.Floc = arena + oF;
-  b.Tc = arena + oTc;
-  b.Ab = arena + oAb;
-  b.gb = arena + ogb;
-  b.Bt = arena + oBt;
-  b.gmaxp = arena + ogm;
-  b.Dc = arena + oD;
-  b.Ec = arena + oE;
-  b.GBc = arena + oG;
-  b.Wc = arena + oW;
-  b.Tau = arena + oTau;
-  b.Ec2 = arena + oE2;
-  b.dL = arena + odL;
-  b.dR = arena + odR;
-  b.dcv = arena + odc;
-  b.part = arena + opart;
-  b.dtau = arena + odt;
-  b.normp = arena + onp;
-  b.graw = arena + ogr;
-  b.gmaxt = arena + ogt;
-  b.normt = arena + ont;
-  b.Fm = arena + oFm;
-  b.Fq = arena + oFq;
-  b.st = (FteState*)(arena + ost);
-  b.bad = (int*)(arena + oint);
-  b.bk = (int*)(arena + obk);
-  b.gdcv = (unsigned long long*)(arena + ogd);
-  // state buffers in one launch (was six copies / fills): host inputs are copied into copy 0
-  // first and the kernel then works in place
-  const double* Xs = X;
-  const double* ts = tau;
-  if (!(flags & ACS_DEVICE_PTRS)) {
-    ACS_HIP(ctx, hipMemcpyAsync(b.X, X, sizeof(double) * M * P, hipMemcpyHostToDevice, s));
-    if (tau) ACS_HIP(ctx, hipMemcpyAsync(b.tau, tau, sizeof(double) * d.NT, hipMemcpyHostToDevice, s));
-    Xs = b.X;
-    ts = tau ? b.tau : nullptr;
-  }
-  const size_t MP = (size_t)M * P;
-  const size_t ngd = (size_t)n * BP * 2 + 64;
-  const size_t nI = std::max(std::max(std::max(MP, (size_t)n + 1), ngd), (size_t)std::max(d.NT, GR));
-  hipLaunchKernelGGL(k_fte_init_state, dim3(acs_grid((int64_t)nI, 256)), dim3(256), 0, s, b.X, Xs, MP, b.tau, ts,
-                     d.NT, b.bad, b.dtau, GR, b.bk, n + 1, b.gdcv, ngd);
-  ACS_HIP(ctx, hipGetLastError());
-  return ACS_OK;
-}
-
-// workgroups per eliminated block of a k_cr_level launch: enough column waves (16 - NB per
-// workgroup), and more of them when few blocks are left (the deep levels are latency-bound):
-// the widest split whose grid still fits the 256 CUs in one wave of workgroups (one
-// 1024-thread workgroup per CU: the LDS is full), one column-block per workgroup when
-// possible, else 6 / 4 / 3 / 2 column-blocks' worth of workgroups per block
-static int cr_nsplit(const FteDims& d, int ne, int ns) {
-  const int NB = d.BP >> 4, NBB = 2 * NB + d.GR / 16;
-  const int need = (NBB + 16 - NB - 1) / (16 - NB);
-  int want = 1;
-  for (int c : {NBB, 6, 4, 3, 2})
-    if (c <= NBB && ne * c + ns <= 256) {
-      want = c;
-      break;
-    }
-  int n = std::min(std::max(need, want), NBB);
-  // two GB column-blocks (GR = 32) over several workgroups: each workgroup's idle column
-  // waves load the GB blocks it does not own (k_cr_level), so keep GRB of them idle
-  const int GRB = d.GR / 16;
-  while (GRB > 1 && n > 1 && n < NBB && 16 - NB - (NBB + n - 1) / n < GRB) ++n;
-  return n;
-}
-
-// Pending-term bookkeeping of one cyclic reduction (k_cr_level): the terms of the levels with
-// steps lo_s .. (current step)/2 have not been applied to the surviving blocks; bit l of
-// symmask: the level of step 2^l stored its D parts as upper tiles.
-struct CrPending {
-  int lo_s = 1;
-  unsigned symmask = 0;
-};
-
-// one k_cr_level launch (template on the tile count NB = BP/16). Returns whether this level's
-// pending Schur terms are stored as upper tiles (the one-wave-per-column-block path; the deep
-// path of k_cr_level writes full tiles).
-static int cr_launch_level(const FteDims& d, hipStream_t s, int sl, int a0, int iend, int top, int ne, int ns,
-                           int astep, const FteState* st, FteBuffers& b, const double* Ein, double* Eout, int* bad,
-                           const CrPending& pend, int l0 = 0, int d_up = 0) {
-  if (ne + ns == 0) return 0;
-  const int NB = d.BP >> 4, NBB = 2 * NB + d.GR / 16;
-  const int nsplit = cr_nsplit(d, ne, ns);
-  const int nwg = ne * nsplit + ns;
-  const size_t lds = sizeof(double) * cr_level_lds_doubles(d.BP, d.GR);
-#define CR_LEVEL_(nb, gb2, dup)                                                                                  \
-  hipLaunchKernelGGL((k_cr_level<nb, gb2, dup>), dim3(nwg), dim3(1024), lds, s, d, sl, a0, iend, top, ne, astep,    \
-                     nsplit, pend.symmask, pend.lo_s, 0, l0, st, b.Dc, Ein, Eout, b.GBc, b.Wc, b.Tau, b.dL, b.dR, bad, \
-                     CrTauSrc{})
-#define CR_LEVEL(nb)                \
-  if (d.GR > 16)                    \
-    CR_LEVEL_(nb, true, false);     \
-  else if (d_up)                    \
-    CR_LEVEL_(nb, false, true);     \
-  else                              \
-    CR_LEVEL_(nb, false, false)
-  switch (NB) {
-    case 1: CR_LEVEL(1); break;
-    case 2: CR_LEVEL(2); break;
-    case 3: CR_LEVEL(3); break;
-    case 4: CR_LEVEL(4); break;
-    case 5: CR_LEVEL(5); break;
-    default: CR_LEVEL(6); break;
-  }
-#undef CR_LEVEL
-#undef CR_LEVEL_
-  return (ne > 0 && !cr_level_deep(d.BP, NBB, nsplit)) ? 1 : 0;
-}
-
-static bool cr_defer() {
-  static const bool v = [] {
-    const char* e = std::getenv("ACS_CR_DEFER");
-    return e && e[0] == '1';
-  }();
-  return v;
-}
-// the single-GPU solve stores D as its upper tiles (k_cr_assemble_build) and levels 0-1 read it
-// so (k_cr_level DUP): constant / no delays (the per-frame-delay mode builds through k_cr_build),
-// one GB column-block (the GB2 instances have no DUP form), survivors not deferred
-// (ACS_D_FULL=1: D stored whole, for A/B timing)
-static bool fte_d_upper(const FteDims& d) {
-  static const bool full = [] {
-    const char* e = std::getenv("ACS_D_FULL");
-    return e && e[0] == '1';
-  }();
-  return !d.var && d.GR <= 16 && !cr_defer() && !full;
-}
-
-// blocks eliminated (ne) and survivors applying the previous level's terms (ns) at the level of
-// step sl of the chain [a0, top]
-static void cr_level_counts(int a0, int iend, int top, int sl, int* ne, int* ns) {
-  *ne = *ns = 0;
-  for (int i = a0 + sl; i < iend; i += 2 * sl) ++*ne;
-  if (sl > 1)
-    for (int j = a0; j <= top; j += 2 * sl) ++*ns;
-}
-
-// Block cyclic reduction of super-blocks [a0, top] (blocks < iend may be eliminated; a
-// chain end at iend survives), nlev levels, then (final_apply) every pending Schur term is
-// applied to the survivors. Survivor workgroups apply the previous level's terms at every
-// level. ACS_CR_DEFER=1 launches them only at a level whose grid then still fits the chip in
-// one wave of workgroups, and the blocks subtract the deferred terms when they are next loaded:
-// at 10,000 frames that saved 26 us at level 1 and cost 30 us at levels 2-4 (each deferred
-// term is one more dependent round of loads, profiles/r05/seq10k_*.log), so it is off.
-// Returns the buffer holding the final couplings E; *pend_out: what is still pending (for the
-// top block).
-static const double* cr_reduce(const FteDims& d, hipStream_t s, const FteState* st, FteBuffers& b, int a0, int iend,
-                               int top, int nlev, int* bad, bool final_apply = true, CrPending* pend_out = nullptr,
-                               bool e_upper = true, bool d_upper = false) {
-  const bool defer = cr_defer();
-  const double* Ein = b.Ec;
-  double* Eout = b.Ec2;
-  CrPending pend;
-  int sl = 1;
-  for (int lv = 0; lv < nlev; ++lv, sl <<= 1) {
-    int ne, ns;
-    cr_level_counts(a0, iend, top, sl, &ne, &ns);
-    if (ns && defer && ne * cr_nsplit(d, ne, ns) + ns > 256) ns = 0;  // defer
-    // level 0 of a chain built by k_cr_assemble_build / k_cr_build: every E is upper triangular.
-    // d_upper (D stored as upper tiles): levels 0 and 1 read D as assembled (the level-1
-    // survivors rewrite theirs whole; every block eliminated later is one of them)
-    const int sym = cr_launch_level(d, s, sl, a0, iend, top, ne, ns, 2 * sl, st, b, Ein, Eout, bad, pend,
-                                    lv == 0 && e_upper ? 1 : 0, d_upper && lv <= 1 ? 1 : 0);
-    if (ns) pend.lo_s = sl;  // the survivors now hold every term of the levels below sl
-    pend.symmask |= (unsigned)sym << lv;
-    double* t = const_cast<double*>(Ein);
-    Ein = Eout;
-    Eout = t;
-  }
-  if (nlev > 0 && final_apply) {
-    int ns = 0;
-    for (int j = a0; j <= top; j += sl) ++ns;
-    cr_launch_level(d, s, sl, a0, iend, top, 0, ns, sl, st, b, Ein, Eout, bad, pend, 0, d_upper && nlev <= 1 ? 1 : 0);
-    pend.lo_s = sl;
-  }
-  if (pend_out) *pend_out = pend;
-  return Ein;
-}
-
-// The single surviving block a0 after nlev levels (step sl = 2^nlev): its pending terms,
-// then W_gb = D^-1 GB and Tau = GB^T W_gb on the register-tiled Gauss-Jordan of k_cr_level
-// (top_mode); k_cr_top finishes with the tau border.
-// with_partials: CR_NCHUNK more workgroups form the tau border partial sums and the frames'
-// |g| max (b.part) meanwhile, for k_cr_back_all (the single-GPU chain, a0 = 0)
-static void cr_launch_top(const FteDims& d, hipStream_t s, int nlev, int a0, int iend, const FteState* st,
-                          FteBuffers& b, int* bad, const CrPending& pend, bool with_partials = false,
-                          int d_up = 0) {
-  const CrTauSrc ts = with_partials ? CrTauSrc{b.Tc, b.gmaxp, b.part} : CrTauSrc{};
-  const int nwg = with_partials ? 1 + CR_NCHUNK : 1;
-  const int sl = 1 << nlev, NB = d.BP >> 4;
-  const size_t lds = sizeof(double) * cr_level_lds_doubles(d.BP, d.GR);
-#define CR_TOP_(nb, gb2, dup)                                                                                        \
-  hipLaunchKernelGGL((k_cr_level<nb, gb2, dup>), dim3(nwg), dim3(1024), lds, s, d, sl, a0, iend, a0, 1, sl, 1,      \
-                     pend.symmask, pend.lo_s, 1, 0, st, b.Dc, b.Ec, b.Ec2, b.GBc, b.Wc, b.Tau, b.dL, b.dR, bad, ts)
-#define CR_TOP(nb)               \
-  if (d.GR > 16)                 \
-    CR_TOP_(nb, true, false);    \
-  else if (d_up)                 \
-    CR_TOP_(nb, false, true);    \
-  else                           \
-    CR_TOP_(nb, false, false)
-  switch (NB) {
-    case 1: CR_TOP(1); break;
-    case 2: CR_TOP(2); break;
-    case 3: CR_TOP(3); break;
-    case 4: CR_TOP(4); break;
-    case 5: CR_TOP(5); break;
-    default: CR_TOP(6); break;
-  }
-#undef CR_TOP
-#undef CR_TOP_
-}
-
-// threads per block of k_cr_assemble_build: the 512-thread instance (compact LDS rows) when the
-// grid is more than one round of 1024-thread blocks, two per CU
-static int cr_asm_threads(int nblk, int n_cu) { return nblk > 2 * n_cu ? 512 : 1024; }
-
-static void cr_launch_assemble_build(const FteDims& d, int n_cu, hipStream_t s, const FteBuffers& b, int b0 = 0,
-                                     int nblk = -1, int lo = 0, int hi = INT_MAX, int end_l = -1, int end_r = -1,
-                                     double* rdiag = nullptr, double* graw = nullptr, int d_full = 0) {
-  if (nblk < 0) nblk = d.nblk;
-  if (nblk <= 0) return;
-  const bool wide = cr_asm_threads(nblk, n_cu) < 1024;
-#define CR_ABUILD_(nb, th)                                                                                  \
-  hipLaunchKernelGGL((k_cr_assemble_build<nb, th>), dim3(nblk), dim3(th), asm_build_lds_bytes(d, th < 1024), s, d, b.X, \
-                     b.qinv, b.st, b.Hloc, b.gloc, b.Dc, b.Ec, b.GBc, b.gmaxp, b0, lo, hi, end_l, end_r, rdiag, graw, \
-                     d_full)
-#define CR_ABUILD(nb)         \
-  if (wide)                   \
-    CR_ABUILD_(nb, 512);      \
-  else                        \
-    CR_ABUILD_(nb, 1024)
-  switch (d.BP >> 4) {
-    case 1: CR_ABUILD(1); break;
-    case 2: CR_ABUILD(2); break;
-    case 3: CR_ABUILD(3); break;
-    case 4: CR_ABUILD(4); break;
-    case 5: CR_ABUILD(5); break;
-    default: CR_ABUILD(6); break;
-  }
-#undef CR_ABUILD
-#undef CR_ABUILD_
-}
-
-static void fte_enqueue_linearize(FteSetup& S, hipStream_t s, int force) {
-  const FteDims& d = S.d;
-  FteBuffers& b = S.b;
-  fte_launch_lin(d, s, b, force, 0, d.N, 0, (double*)nullptr, (const double*)nullptr);
-  hipLaunchKernelGGL(k_fte_assemble, dim3(d.M), dim3(256), 0, s, d, b.X, b.tau, b.qinv, b.st, force, 0, 0, INT_MAX,
-                     b.Hloc, b.gloc, b.Ab, b.gb, b.Bt, b.gmaxp, b.Adiag, 1);
-}
-
-// one LM iteration: linearise (if the last step was accepted), cyclic-reduction solve,
-// trial state, exact cost, accept/reject — all device-resident, no host round trip
-static void fte_enqueue_iteration(FteSetup& S, hipStream_t s, const FteOptsDev& o) {
-  const FteDims& d = S.d;
-  FteBuffers& b = S.b;
-  // the linearisation of X[cur] is already there (initial, or speculative at the last
-  // accepted trial): assemble the banded rows and build the damped super-blocks (variable
-  // delays: assembled when new or re-eliminated for a new damping, then built)
-  if (d.var) {
-    hipLaunchKernelGGL(k_fte_assemble, dim3(d.M), dim3(256), 0, s, d, b.X, b.tau, b.qinv, b.st, 0, 0, 0, INT_MAX,
-                       b.Hloc, b.gloc, b.Ab, b.gb, b.Bt, b.gmaxp, b.Adiag, 1);
-    cr_launch_build(d, s, d.nblk, b.st, b.Ab, b.gb, b.Bt, b.Dc, b.Ec, b.GBc, 0, -1, -1, b.Adiag);
-  } else {
-    cr_launch_assemble_build(d, S.n_cu, s, b, 0, -1, 0, INT_MAX, -1, -1, nullptr, nullptr,
-                             fte_d_upper(d) ? 0 : 1);
-  }
-  const int bend = d.nblk - 1;
-  CrPending pend;
-  // D stored as upper tiles by k_cr_assemble_build (constant / no delays; the per-frame-delay
-  // mode builds through k_cr_build, whole): read as assembled by levels 0-1 and by the top block
-  // when no survivor ever rewrote it (nlev <= 1); off with ACS_CR_DEFER (survivors deferred)
-  const bool dup = fte_d_upper(d);
-  cr_reduce(d, s, b.st, b, 0, d.nblk, d.nblk - 1, d.nlev, b.bad, false, &pend, true, dup);
-  cr_launch_top(d, s, d.nlev, 0, d.nblk, b.st, b, b.bad, pend, true, dup && d.nlev <= 1 ? 1 : 0);
-  // the top block and every back-substitution level in one launch, chained by
-  // per-launch stamps (running the top levels' few blocks one after the other inside one
-  // workgroup was tried in r03 and took 30 us: one workgroup streams a block's W at ~2 us, so
-  // the W loads of every block have to be in flight at once). Constant / no delays: the
-  // trial state is stepped there too; variable delays need the neighbours' rows: k_cr_trial
-  double* Xt = d.var ? nullptr : b.X;
-  // 8 lanes per row of a block (cr_back_block): 640 threads at BP = 80, so two workgroups
-  // share a CU (91 VGPRs, 5 waves per SIMD) and one's W loads overlap the other's wait
-  // (template sizes: the columns each lane of a row holds, BP / 8 and GR / 8, no padding)
-  const int nth_back = (8 * d.BP + 63) / 64 * 64;
-  // blocks of levels >= late_lv wait for their inputs before loading W (ACS_BACK_LATE_LV; 30: never)
-  static const int late_lv = [] {
-    const char* e = std::getenv("ACS_BACK_LATE_LV");
-    const int v = e ? std::atoi(e) : 30;
-    return v < 0 ? 0 : (v > 30 ? 30 : v);  // k_cr_back_all shifts 1 << late_lv
-  }();
-#define CR_BACK_ALL(nb, grb)                                                                                   \
-  hipLaunchKernelGGL((k_cr_back_all<nb, grb>), dim3(d.nblk), dim3(nth_back), 0, s, d, bend, b.st,  \
-                     (const double*)b.Wc, (const double*)b.Tau, (const double*)b.part, (const double*)b.gmaxp, \
-                     b.tau, b.dtau, b.dcv, b.bk, b.gdcv,    \
-                     b.bad, Xt, b.normp, late_lv)
-#define CR_BACK_ALL_G(nb) \
-  if (d.GR <= 16)         \
-    CR_BACK_ALL(nb, 1);   \
-  else                    \
-    CR_BACK_ALL(nb, 2)
-  switch (d.BP >> 4) {
-    case 1: CR_BACK_ALL_G(1); break;
-    case 2: CR_BACK_ALL_G(2); break;
-    case 3: CR_BACK_ALL_G(3); break;
-    case 4: CR_BACK_ALL_G(4); break;
-    case 5: CR_BACK_ALL_G(5); break;
-    default: CR_BACK_ALL_G(6); break;
-  }
-#undef CR_BACK_ALL_G
-#undef CR_BACK_ALL
-  if (d.var)
-    hipLaunchKernelGGL(k_cr_trial, dim3(d.nblk), dim3(256), 0, s, d, b.st, b.dcv, b.dtau, b.Hloc, b.gloc, b.X, b.tau,
-                       b.normp, 1, 0, 1);
-  // speculative linearisation at the trial state: its measurement terms and the model terms
-  // are the trial cost (no separate cost pass)
-  fte_launch_lin(d, s, b, 0, 0, d.N, 1, b.Fq, b.qinv);
-  hipLaunchKernelGGL(k_fte_lm, dim3(1), dim3(FTE_LM_THREADS), 0, s, d, b.st, o, 0, b.Floc, b.Fq, b.normp, 1, S.snap);
-}
-
-// =======================================================================================
-// frame-window distributed solve (spec: oracle/fte_dist.py)
-//
-// Super-blocks are split into R chains [a_r, a_r + 2^k] that share their end blocks
-// (a_r = r 2^k; blocks past the sequence are phantoms). A term is owned by the chain
-// containing its lowest row, so every term is counted on exactly one rank and the
-// chain-end blocks hold partial sums. Per LM iteration:
-//   phase 1  linearise owned frames, assemble chain rows, block cyclic reduction of the
-//            chain interior down to its two ends (ends undamped), pack the ends' blocks,
-//            raw diagonals / gradients, tau partial sums and an interior |g| max into
-//            payload 1 (zeros elsewhere)                                 -> all-reduce
-//   phase 2  every rank: reduced block-tridiagonal system over the R+1 chain ends + tau
-//            (damped with the summed raw diagonals), solved with the same CR kernels;
-//            back substitution down its own chain; its rows of delta into payload 2
-//                                                                        -> all-reduce
-//   phase 3  trial state on every rank (replicated X), cost of the owned terms
-//                                                        -> all-reduce (2 doubles)
-//   phase 4  the same accept/reject decision on every rank
-// =======================================================================================
-struct DistLayout {
-  size_t oD, oE, oG, oGraw, oRdiag, oTau, oGmax, n1, n2, n3;
-};
-
-static DistLayout dist_layout(const FteDims& d, int R) {
-  DistLayout L;
-  const size_t nb = R + 1, BP = d.BP, GR = d.GR, nE = (size_t)d.Cg * d.Cg + d.Cg + (size_t)GR * GR;
-  L.oD = 0;
-  L.oE = L.oD + nb * BP * BP;
-  L.oG = L.oE + nb * BP * BP;
-  L.oGraw = L.oG + nb * BP * GR;
-  L.oRdiag = L.oGraw + nb * BP;
-  L.oTau = L.oRdiag + nb * BP;
-  L.oGmax = L.oTau + nE;
-  L.n1 = L.oGmax + R;
-  L.n2 = (size_t)d.nblk * BP + (d.var ? (size_t)d.NT : 0);  // solution rows (+ per-frame delays)
-  L.n3 = 4;
-  return L;
-}
-
-// chain ends -> payload slots `rank` (left end a0) and `rank + 1` (right end bend)
-__global__ __launch_bounds__(256) void k_dist_pack(FteDims d, const FteState* __restrict__ st, DistLayout Lo,
-                                                   int rank, int a0, int bend, const double* __restrict__ Dc,
-                                                   const double* __restrict__ Ec, const double* __restrict__ GBc,
-                                                   const double* __restrict__ rdiag, const double* __restrict__ gb,
-                                                   double* __restrict__ p1) {
-  if (st->status != 0) return;
-  const int side = blockIdx.y;  // 0 left end, 1 right end
-  const int blk = side ? bend : a0, q = rank + side;
-  if (blk >= d.nblk) return;
-  const int BP = d.BP, GR = d.GR, P = d.P;
-  const size_t nBB = (size_t)BP * BP;
-  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < nBB; e += (size_t)gridDim.x * blockDim.x) {
-    p1[Lo.oD + q * nBB + e] = Dc[(size_t)blk * nBB + e];
-    if (side) p1[Lo.oE + q * nBB + e] = Ec[(size_t)blk * nBB + e];
-  }
-  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < (size_t)BP * GR;
-       e += (size_t)gridDim.x * blockDim.x)
-    p1[Lo.oG + (size_t)q * BP * GR + e] = GBc[(size_t)blk * BP * GR + e];
-  if (blockIdx.x == 0) {
-    for (int r = threadIdx.x; r < BP; r += blockDim.x) {
-      const int fr = 3 * blk + r / P, pr = r % P;
-      const bool in = r < 3 * P && fr < d.M;
-      p1[Lo.oGraw + (size_t)q * BP + r] = in ? gb[(size_t)fr * P + pr] : 0.0;
-      p1[Lo.oRdiag + (size_t)q * BP + r] = in ? rdiag[(size_t)fr * P + pr] : 0.0;
-    }
-  }
-}
-
-// tau partial sums of the chain (fixed chunk order) and the |g| max of its interior rows
-__global__ __launch_bounds__(256) void k_dist_pack_small(FteDims d, const FteState* __restrict__ st, DistLayout Lo,
-                                                         int rank, int a0, int bend,
-                                                         const double* __restrict__ part,
-                                                         const double* __restrict__ gmaxp,
-                                                         double* __restrict__ p1,
-                                                         const double* __restrict__ gmaxt = nullptr) {
-  if (st->status != 0) return;
-  __shared__ double s_red[256];
-  const int nE = d.Cg * d.Cg + d.Cg + d.GR * d.GR;
-  for (int e = threadIdx.x; e < nE; e += blockDim.x) {
-    double v = 0.0;
-    for (int ch = 0; ch < CR_NCHUNK; ++ch) v += part[(size_t)ch * nE + e];
-    p1[Lo.oTau + e] = v;
-  }
-  const int f0 = 3 * (a0 + 1), f1 = min(3 * min(bend, d.nblk), d.M);
-  double mx = 0.0;
-  mx = strided_max(gmaxp, f0 + (int)threadIdx.x, f1, blockDim.x, mx);
-  // per-frame delays: every owned frame's (rows of the whole chain; other frames give 0)
-  if (gmaxt) mx = strided_max(gmaxt, 3 * a0 + (int)threadIdx.x, min(3 * min(bend, d.nblk - 1) + 3, d.M), blockDim.x, mx);
-  mx = block_max(mx, s_red);
-  if (threadIdx.x == 0) p1[Lo.oGmax + rank] = mx;
-}
-
-// reduced system over the chain ends e_q = q 2^k (q = 0..R) from the summed payload
-__global__ __launch_bounds__(256) void k_red_build(FteDims d, const FteState* __restrict__ st, DistLayout Lo, int R,
-                                                   int span, const double* __restrict__ p1, double* __restrict__ Dr,
-                                                   double* __restrict__ Er, double* __restrict__ GBr,
-                                                   double* __restrict__ gmaxr) {
-  if (st->status != 0) return;
-  __shared__ double s_red[256];
-  const int q = blockIdx.x, e = q * span;
-  const int BP = d.BP, GR = d.GR, P = d.P;
-  const size_t nBB = (size_t)BP * BP;
-  const double lam = st->lam;
-  // rows of block x that are real unknowns (not padding / phantom)
-  auto live = [&](int x, int r) { return x >= 0 && x < d.nblk && r < 3 * P && 3 * x + r / P < d.M; };
-  for (size_t x = threadIdx.x; x < nBB; x += blockDim.x) {
-    const int r = (int)(x / BP), c = (int)(x % BP);
-    double v = (r == c) ? 1.0 : 0.0;
-    if (live(e, r) && live(e, c)) {
-      v = p1[Lo.oD + q * nBB + x];
-      if (r == c) v += lam * fmax(p1[Lo.oRdiag + (size_t)q * BP + r], 1e-12);
-    }
-    Dr[q * nBB + x] = v;
-    Er[q * nBB + x] = (q > 0 && live(e, r) && live(e - span, c)) ? p1[Lo.oE + q * nBB + x] : 0.0;
-  }
-  for (size_t x = threadIdx.x; x < (size_t)BP * GR; x += blockDim.x) {
-    const int r = (int)(x / GR);
-    GBr[(size_t)q * BP * GR + x] = live(e, r) ? p1[Lo.oG + (size_t)q * BP * GR + x] : 0.0;
-  }
-  if (q == 0) {
-    double mx = 0.0;
-    for (int t = threadIdx.x; t < R; t += blockDim.x) mx = fmax(mx, p1[Lo.oGmax + t]);
-    for (int t = threadIdx.x; t < (R + 1) * BP; t += blockDim.x) {
-      const int qq = t / BP, r = t % BP, ee = qq * span;
-      if (ee < d.nblk && r < 3 * P && 3 * ee + r / P < d.M) mx = fmax(mx, fabs(p1[Lo.oGraw + t]));
-    }
-    mx = block_max(mx, s_red);
-    if (threadIdx.x == 0) gmaxr[0] = mx;
-  }
-}
-
-__global__ void k_red_part(int nE, const DistLayout Lo, const FteState* __restrict__ st,
-                           const double* __restrict__ p1, double* __restrict__ partr) {
-  if (st->status != 0) return;
-  for (int e = threadIdx.x; e < nE; e += blockDim.x) partr[e] += p1[Lo.oTau + e];
-}
-
-__global__ void k_dist_scatter(FteDims d, const FteState* __restrict__ st, int rank, int a0, int bend,
-                               const double* __restrict__ dcvr, double* __restrict__ dcv) {
-  if (st->status != 0) return;
-  for (int r = threadIdx.x; r < d.BP; r += blockDim.x) {
-    if (a0 < d.nblk) dcv[(size_t)a0 * d.BP + r] = dcvr[(size_t)rank * d.BP + r];
-    if (bend < d.nblk) dcv[(size_t)bend * d.BP + r] = dcvr[(size_t)(rank + 1) * d.BP + r];
-  }
-}
-
-// p3 = (measurement cost, model cost, |step|^2, |X, tau|^2) of this rank's owned terms /
-// rows (frames [k0, k1), super-blocks [n0, n1) of the trial's norm partials)
-// which = 1: the trial's measurement terms are in Fm's speculative copy (cur ^ 1, N each)
-__global__ __launch_bounds__(256) void k_dist_cost_pack(FteState* __restrict__ st, int which, int N, int m0,
-                                                        int m1, int q0, int q1, const double* __restrict__ Fm,
-                                                        const double* __restrict__ Fq, int n0, int n1,
-                                                        const double* __restrict__ normp, double* __restrict__ p3,
-                                                        int t0 = 0, int t1 = 0,
-                                                        const double* __restrict__ normt = nullptr) {
-  if (which == 1 && st->status != 0) return;
-  if (which == 1) Fm += (size_t)(st->cur ^ 1) * N;
-  __shared__ double s_red[256];
-  double a = 0.0, b = 0.0, nrm[2] = {0.0, 0.0};
-  {
-    const double* xs[1] = {Fm};
-    strided_sums<1>(xs, 1, m0 + (int)threadIdx.x, m1, blockDim.x, &a);
-  }
-  {
-    const double* xs[1] = {Fq};
-    strided_sums<1>(xs, 1, q0 + (int)threadIdx.x, q1, blockDim.x, &b);
-  }
-  if (n1 > n0) {
-    const double* xs[2] = {normp, normp + 1};
-    strided_sums<2>(xs, 2, n0 + (int)threadIdx.x, n1, blockDim.x, nrm);
-  }
-  if (normt && t1 > t0) {  // per-frame delays of the owned frames, over every block of the chain
-    const double* xs[2] = {normt, normt + 1};
-    strided_sums<2>(xs, 2, t0 + (int)threadIdx.x, t1, blockDim.x, nrm);
-  }
-  double dn = nrm[0], xn = nrm[1];
-  a = block_sum(a, s_red);
-  b = block_sum(b, s_red);
-  dn = block_sum(dn, s_red);
-  xn = block_sum(xn, s_red);
-  if (threadIdx.x == 0) {
-    p3[0] = a;
-    p3[1] = b;
-    p3[2] = dn;
-    p3[3] = xn;
-    if (which == 1) st->pending = 1;  // this round took a step: its cost travels in p3
-  }
-}
-
-// X[cur] rows of super-blocks [b_lo, b_hi) in the block layout of the step (BP per block);
-// per-frame delays: those of the owned frames [k_lo, k_hi) after the rows
-__global__ __launch_bounds__(256) void k_dist_x_out(FteDims d, const FteState* __restrict__ st, int b_lo, int b_hi,
-                                                    const double* __restrict__ Xbuf, double* __restrict__ p2,
-                                                    const double* __restrict__ taubuf, int k_lo, int k_hi) {
-  const double* X = Xbuf + (size_t)st->cur * d.M * d.P;
-  const int P = d.P, BP = d.BP;
-  for (size_t e = (size_t)b_lo * BP + (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < (size_t)b_hi * BP;
-       e += (size_t)gridDim.x * blockDim.x) {
-    const int i = (int)(e / BP), r = (int)(e % BP), f = 3 * i + r / P;
-    if (r < 3 * P && f < d.M) p2[e] = X[(size_t)f * P + r % P];
-  }
-  if (d.var) {
-    const double* tau = taubuf + (size_t)st->cur * d.NT;
-    for (size_t e = (size_t)k_lo * d.C + (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < (size_t)k_hi * d.C;
-         e += (size_t)gridDim.x * blockDim.x)
-      p2[(size_t)d.nblk * BP + e] = tau[e];
-  }
-}
-
-// every row of X[cur] (and every per-frame delay) from the gathered layout
-__global__ __launch_bounds__(256) void k_dist_x_in(FteDims d, const FteState* __restrict__ st,
-                                                   const double* __restrict__ p2, double* __restrict__ Xbuf,
-                                                   double* __restrict__ taubuf) {
-  double* X = Xbuf + (size_t)st->cur * d.M * d.P;
-  const int P = d.P, BP = d.BP;
-  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < (size_t)d.nblk * BP;
-       e += (size_t)gridDim.x * blockDim.x) {
-    const int i = (int)(e / BP), r = (int)(e % BP), f = 3 * i + r / P;
-    if (r < 3 * P && f < d.M) X[(size_t)f * P + r % P] = p2[e];
-  }
-  if (d.var) {
-    double* tau = taubuf + (size_t)st->cur * d.NT;
-    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < (size_t)d.NT; e += (size_t)gridDim.x * blockDim.x)
-      tau[e] = p2[(size_t)d.nblk * BP + e];
-  }
-}
-
-// Round control (one thread). On the summed payload of the previous round: the first round
-// takes the initial cost; otherwise a pending step is accepted or rejected (oracle/fte.py
-// solve; every rank takes the same decision). A rejection marks the round SKIP: its solve
-// is stale (formed for the trial state) and the round only re-forms the reduced system.
-__global__ void k_dist_decide(FteState* __restrict__ st, FteOptsDev o, const double* __restrict__ p3) {
-  if (threadIdx.x != 0) return;
-  const double fm = p3[0], fq = p3[1];
-  if (st->first) {
-    st->first = 0;
-    st->F = st->F0 = fm + fq;
-    st->Fmeas = fm;
-    st->Fmodel = fq;
-    // max_iters = 0: no step at all, as acs_fte_solve (X0 back, iters 0)
-    if (o.max_iters <= 0) st->status = ACS_STATUS_MAXITER;
-    return;
-  }
-  if (st->status != 0 || !st->pending) return;
-  st->pending = 0;
-  const double Fn = fm + fq, dn = p3[2], xn = p3[3];  // step / state norms summed over the owned rows
-  st->iters += 1;
-  st->dnorm = sqrt(dn);
-  st->xnorm = sqrt(xn);
-  const bool small = sqrt(dn) <= o.xtol * (o.xtol + sqrt(xn));
-  if (Fn < st->F) {
-    const bool fconv = (st->F - Fn) <= o.ftol * fabs(st->F);
-    st->nacc += 1;
-    st->F = Fn;
-    st->Fmeas = fm;
-    st->Fmodel = fq;
-    st->cur ^= 1;
-    st->lam = fmax(st->lam * 0.1, 1e-15);
-    st->relin = 1;
-    if (fconv)
-      st->status = ACS_STATUS_FTOL;
-    else if (small)
-      st->status = ACS_STATUS_XTOL;
-  } else {
-    st->lam *= 10.0;
-    st->relin = 0;
-    if (st->lam > 1e16) st->status = ACS_STATUS_STALLED;
-  }
-  if (st->status == 0 && st->iters >= o.max_iters) st->status = ACS_STATUS_MAXITER;
-  if (st->status == 0 && !st->relin) st->status = FTE_STATUS_SKIP;
-}
-
-// after the reduced solve of a live round: the gradient test on the summed gradient
-__global__ void k_dist_gtol(FteState* __restrict__ st, FteOptsDev o) {
-  if (threadIdx.x == 0 && st->status == 0 && st->gmax <= o.gtol) st->status = ACS_STATUS_GTOL;
-}
-
-// before / after the round's reduced system: a round that took a step forms it at the trial
-// state (copy cur ^ 1, linearised there for the trial cost) with the damping an acceptance
-// sets; the LM state is swapped for those kernels and restored after them
-__global__ void k_dist_spec(FteState* __restrict__ st, int enter) {
-  if (threadIdx.x != 0) return;
-  if (enter) {
-    if (st->status == FTE_STATUS_SKIP) st->status = 0;
-    if (st->status == 0 && st->pending) {
-      st->spec_on = 1;
-      st->save_cur = st->cur;
-      st->save_lam = st->lam;
-      st->cur ^= 1;
-      st->lam = fmax(st->lam * 0.1, 1e-15);
-    }
-  } else if (st->spec_on) {
-    st->spec_on = 0;
-    st->cur = st->save_cur;
-    st->lam = st->save_lam;
-  }
-}
-
-struct acs_fte_dist {
-  acs_ctx* ctx;
-  FteSetup S;
-  void* own = nullptr;
-  void* own_red = nullptr;
-  FteDims dr;        // reduced system dims (R + 1 blocks)
-  FteBuffers r;      // reduced arrays (Dc, Ec, GBc, Wc, Tau, dcv, part, gmaxp)
-  DistLayout Lo;
-  FteOptsDev o;
-  int R, rank, span, a0, bend, klev;
-  double lam0;  // the LM's initial damping (acs_fte_dist_reset restarts from it)
-  int k_lo, k_hi, f_lo, f_hi, b_hi_build, c_lo, c_hi, own_lo, own_hi, out_lo, out_hi;
-  // rounds captured as hipGraphs (one graph launch instead of ~60 kernel launches); key =
-  // (input payload, output payload, stream): two graphs for the two payload buffers
-  struct Captured {
-    hipGraphExec_t exec = nullptr;
-    const void* ptr = nullptr;
-    const void* ptr2 = nullptr;
-    hipStream_t stream = nullptr;
-  } g[2];
-  // status after each round: pinned ring of ACS_DIST_RING slots with completion events
-  int32_t* snap = nullptr;
-  hipEvent_t snap_ev[4] = {};
-  int64_t rounds = 0;
-};
-#define ACS_DIST_RING 4
-
-// Run `enqueue` (kernel launches on ctx->stream) through the phase's cached graph,
-// capturing it when the key changed; plain launches if capture is unavailable.
-template <typename F>
-static int dist_run_captured(acs_fte_dist* h, const void* ptr, const void* ptr2, F enqueue) {
-  acs_ctx* ctx = h->ctx;
-  hipStream_t s = ctx->stream;
-  int which = 0;
-  for (; which < 2; ++which)
-    if (h->g[which].exec && h->g[which].ptr == ptr && h->g[which].ptr2 == ptr2 && h->g[which].stream == s) break;
-  if (which == 2) which = (h->g[0].exec && !h->g[1].exec) ? 1 : 0;
-  auto& c = h->g[which];
-  if (!c.exec || c.ptr != ptr || c.ptr2 != ptr2 || c.stream != s) {
-    if (c.exec) (void)hipGraphExecDestroy(c.exec);
-    c.exec = nullptr;
-    hipGraph_t graph = nullptr;
-    if (hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed) == hipSuccess) {
-      const int rc = enqueue();
-      const hipError_t e = hipStreamEndCapture(s, &graph);
-      if (rc) {
-        if (graph) (void)hipGraphDestroy(graph);
-        return rc;
-      }
-      if (e == hipSuccess && graph && hipGraphInstantiate(&c.exec, graph, nullptr, nullptr, 0) == hipSuccess) {
-        c.ptr = ptr;
-        c.ptr2 = ptr2;
-        c.stream = s;
-      } else {
-        c.exec = nullptr;
-      }
-      if (graph) (void)hipGraphDestroy(graph);
-    }
-    if (!c.exec) {
-      (void)hipGetLastError();
-      return enqueue();
-    }
-  }
-  ACS_HIP(ctx, hipGraphLaunch(c.exec, s));
-  return ACS_OK;
-}
-
-static const double* dist_local_cr(acs_fte_dist* h) {
-  const FteDims& d = h->S.d;
-  FteBuffers& b = h->S.b;
-  const int top = std::min(h->bend, d.nblk - 1);  // last existing block of the chain
-  return cr_reduce(d, h->ctx->stream, b.st, b, h->a0, std::min(h->bend, d.nblk), top, h->klev, b.bad);
-}
-
+// ---------------------------------------------------------------------------------------
+// single-GPU entry points (include/acinoset_hip.h)
+// ---------------------------------------------------------------------------------------
 // Wait until the solve loop's iteration count in the pinned word after the two snapshot
 // slots (fte_snapshot) reaches `want`. The stream is queried now and then, so a failed or
 // drained stream ends the wait with an error instead of a hang.
@@ -3855,26 +2992,20 @@ int acs_fte_solve(acs_ctx* ctx, const int32_t* skel_ints, int64_t n_ints, const 
   acs_fte_default_opts(&op);
   if (opts) op = *opts;
   ACS_CHECK(ctx, op.max_iters >= 0, "fte: max_iters < 0");
+  const FteProblem pb{skel_ints, n_ints, skel_reals, n_reals, cams, n_cams, meas, w, n_frames, shutter_delay, Ts, qinv,
+                      sd_mode, intermode, X, tau, flags, op.redesc_a, op.redesc_b, op.redesc_c};
   FteSetup S;
   int rc;
-  if ((rc = fte_setup(ctx, S, skel_ints, n_ints, skel_reals, n_reals, cams, n_cams, meas, w, n_frames, shutter_delay,
-                      Ts, qinv, sd_mode, intermode, X, tau, op.redesc_a, op.redesc_b, op.redesc_c, flags)))
-    return rc;
+  if ((rc = fte_setup(ctx, S, pb))) return rc;
   const FteDims& d = S.d;
   FteBuffers& b = S.b;
   hipStream_t s = ctx->stream;
-  FteState st0;
-  std::memset(&st0, 0, sizeof(st0));
-  st0.lam = op.lambda0;
-  st0.relin = 1;
-  ACS_HIP(ctx, hipMemcpyAsync(b.st, &st0, sizeof(st0), hipMemcpyHostToDevice, s));
+  if ((rc = fte_upload_state(ctx, S, op.lambda0))) return rc;
   FteOptsDev o{op.max_iters, op.ftol, op.xtol, op.gtol};
-  hipLaunchKernelGGL(k_fte_cost, dim3(d.N), dim3(64), 0, s, d, b.I, b.Rl, b.cams, b.meas, b.w, b.X, b.tau, b.qinv,
-                     b.st, 0, 0, 0, INT_MAX, b.Fm, b.Fq);
+  fte_launch_cost(d, s, b);
   hipLaunchKernelGGL(k_fte_lm, dim3(1), dim3(FTE_LM_THREADS), 0, s, d, b.st, o, 1, b.Fm, b.Fq, b.normp, 0);
   // the linearisation of the initial state (buffer cur = 0); later ones are speculative
-  if (op.max_iters > 0)
-    fte_launch_lin(d, s, b, 1, 0, d.N, 0, (double*)nullptr, (const double*)nullptr);
+  if (op.max_iters > 0) fte_launch_lin(d, s, b, 1, 0, d.N);
   ACS_HIP(ctx, hipGetLastError());
   // enqueue the iterations one ahead of the host: the host reads iteration n's status
   // snapshot (pinned slot n & 1, published with its iteration count, fte_snapshot) while
@@ -3914,25 +3045,7 @@ int acs_fte_solve(acs_ctx* ctx, const int32_t* skel_ints, int64_t n_ints, const 
     ACS_HIP(ctx, hipMemcpyAsync(&hs, b.st, sizeof(hs), hipMemcpyDeviceToHost, s));
     ACS_HIP(ctx, hipStreamSynchronize(s));
   }
-  const hipMemcpyKind kout = (flags & ACS_DEVICE_PTRS) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-  ACS_HIP(ctx, hipMemcpyAsync(X, b.X + (size_t)hs.cur * d.M * d.P, sizeof(double) * d.M * d.P, kout, s));
-  if (tau) ACS_HIP(ctx, hipMemcpyAsync(tau, b.tau + (size_t)hs.cur * d.NT, sizeof(double) * d.NT, kout, s));
-  int nbad = 0;
-  ACS_HIP(ctx, hipMemcpyAsync(&nbad, b.bad, sizeof(int), hipMemcpyDeviceToHost, s));
-  ACS_HIP(ctx, hipStreamSynchronize(s));
-  if (report) {
-    report->status = hs.status == 0 ? ACS_STATUS_MAXITER : hs.status;
-    report->iters = hs.iters;
-    report->n_accepted = hs.nacc;
-    report->n_bad_pivots = nbad;
-    report->cost_before = hs.F0;
-    report->cost_after = hs.F;
-    report->cost_meas = hs.Fmeas;
-    report->cost_model = hs.Fmodel;
-    report->grad_max = hs.gmax;
-    report->lambda_final = hs.lam;
-  }
-  return ACS_OK;
+  return fte_read_result(ctx, S, hs, X, tau, report, flags);
 }
 
 // Cost, gradient and (optionally) the dense undamped normal matrix at (X, tau): the
@@ -3944,21 +3057,17 @@ int acs_fte_eval(acs_ctx* ctx, const int32_t* skel_ints, int64_t n_ints, const d
   ACS_DEVICE_GUARD(ctx);
   ACS_FISHEYE_ONLY(ctx, flags, "acs_fte_eval");
   ACS_CHECK(ctx, !(flags & ACS_DEVICE_PTRS), "acs_fte_eval takes host pointers");
+  const FteProblem pb{skel_ints, n_ints, skel_reals, n_reals, cams, n_cams, meas, w, n_frames, shutter_delay, Ts, qinv,
+                      sd_mode, intermode, X, tau, 0};
   FteSetup S;
   int rc;
-  if ((rc = fte_setup(ctx, S, skel_ints, n_ints, skel_reals, n_reals, cams, n_cams, meas, w, n_frames, shutter_delay,
-                      Ts, qinv, sd_mode, intermode, X, tau, 3.0, 10.0, 20.0, 0)))
-    return rc;
+  if ((rc = fte_setup(ctx, S, pb))) return rc;
   const FteDims& d = S.d;
   FteBuffers& b = S.b;
   hipStream_t s = ctx->stream;
-  FteState st0;
-  std::memset(&st0, 0, sizeof(st0));
-  st0.relin = 1;
-  ACS_HIP(ctx, hipMemcpyAsync(b.st, &st0, sizeof(st0), hipMemcpyHostToDevice, s));
+  if ((rc = fte_upload_state(ctx, S, 0.0))) return rc;
   fte_enqueue_linearize(S, s, 1);
-  hipLaunchKernelGGL(k_fte_cost, dim3(d.N), dim3(64), 0, s, d, b.I, b.Rl, b.cams, b.meas, b.w, b.X, b.tau, b.qinv,
-                     b.st, 0, 0, 0, INT_MAX, b.Fm, b.Fq);
+  fte_launch_cost(d, s, b);
   ACS_HIP(ctx, hipGetLastError());
   const int M = d.M, P = d.P, Cg = d.Cg, N = d.N, PP = P * P;
   std::vector<double> Ab((size_t)M * 4 * PP), gb((size_t)M * P), Bt((size_t)M * P * (Cg ? Cg : 1)),
@@ -4051,25 +3160,22 @@ int acs_fte_debug_blocks(acs_ctx* ctx, const int32_t* skel_ints, int64_t n_ints,
   ACS_FISHEYE_ONLY(ctx, flags, "acs_fte_debug_blocks");
   ACS_CHECK(ctx, D_out && levels >= 0, "acs_fte_debug_blocks: null D_out or levels < 0");
   ACS_CHECK(ctx, !(shutter_delay && sd_mode == 1), "acs_fte_debug_blocks: constant or no shutter delay only");
+  const FteProblem pb{skel_ints, n_ints, skel_reals, n_reals, cams, n_cams, meas, w, n_frames, shutter_delay, Ts, qinv,
+                      sd_mode, intermode, X, tau, flags};
   FteSetup S;
   int rc;
-  if ((rc = fte_setup(ctx, S, skel_ints, n_ints, skel_reals, n_reals, cams, n_cams, meas, w, n_frames, shutter_delay,
-                      Ts, qinv, sd_mode, intermode, X, tau, 3.0, 10.0, 20.0, flags)))
-    return rc;
+  if ((rc = fte_setup(ctx, S, pb))) return rc;
   const FteDims& d = S.d;
   FteBuffers& b = S.b;
   hipStream_t s = ctx->stream;
-  FteState st0;
-  std::memset(&st0, 0, sizeof(st0));
-  st0.lam = lam;
-  st0.relin = 1;
-  ACS_HIP(ctx, hipMemcpyAsync(b.st, &st0, sizeof(st0), hipMemcpyHostToDevice, s));
-  fte_launch_lin(d, s, b, 1, 0, d.N, 0, (double*)nullptr, (const double*)nullptr);
+  if ((rc = fte_upload_state(ctx, S, lam))) return rc;
+  fte_launch_lin(d, s, b, 1, 0, d.N);
   const int L = std::min((int)levels, d.nlev);
   // as the solve stores it (upper tiles) unless the assembled D itself is asked for
-  cr_launch_assemble_build(d, S.n_cu, s, b, 0, -1, 0, INT_MAX, -1, -1, nullptr, nullptr,
-                           L == 0 || !fte_d_upper(d) ? 1 : 0);
-  if (L > 0) cr_reduce(d, s, b.st, b, 0, d.nblk, d.nblk - 1, L, b.bad, true, nullptr, true, fte_d_upper(d));
+  cr_launch_assemble_build(d, S.n_cu, s, b, L == 0 || !fte_d_upper(d) ? 1 : 0);
+  CrReduceOpts ro;
+  ro.d_upper = fte_d_upper(d);
+  if (L > 0) cr_reduce(d, s, b, 0, d.nblk, d.nblk - 1, L, ro);
   ACS_HIP(ctx, hipGetLastError());
   const size_t bytes = sizeof(double) * (size_t)d.nblk * d.BP * d.BP;
   ACS_HIP(ctx, hipMemcpyAsync(D_out, b.Dc, bytes, (flags & ACS_DEVICE_PTRS) ? hipMemcpyDeviceToDevice
@@ -4125,441 +3231,4 @@ void acs_fte_back_trace_read(unsigned long long* out) {
   (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_back_trace), sizeof(g_back_trace));
 }
 #endif
-}  // extern "C"
-
-// acs_fte_covariance: selected inversion of the undamped normal matrix (its own kernels)
-#include "fte_cov.hpp"
-
-// ---------------------------------------------------------------------------------------
-// distributed handle API (include/acinoset_hip.h, §8(e)); payloads are device pointers
-// ---------------------------------------------------------------------------------------
-extern "C" {
-
-int acs_fte_dist_create(acs_ctx* ctx, const int32_t* skel_ints, int64_t n_ints, const double* skel_reals,
-                        int64_t n_reals, const double* cams, int32_t n_cams, const double* meas, const double* w,
-                        int32_t n_frames, int32_t shutter_delay, double Ts, const double* qinv, int32_t sd_mode,
-                        int32_t intermode, const double* X, const double* tau, const acs_fte_opts* opts, int32_t rank,
-                        int32_t world, acs_fte_dist** out, int64_t* payload_sizes, uint32_t flags) {
-  ACS_DEVICE_GUARD(ctx);
-  ACS_FISHEYE_ONLY(ctx, flags, "acs_fte_dist_create");
-  acs_fte_opts op;
-  acs_fte_default_opts(&op);
-  if (opts) op = *opts;
-  ACS_CHECK(ctx, op.max_iters >= 0, "fte: max_iters < 0");
-  ACS_CHECK(ctx, world >= 1 && world <= 1024 && rank >= 0 && rank < world, "fte_dist: rank %d / world %d", rank,
-            world);
-  acs_fte_dist* h = new acs_fte_dist();
-  h->ctx = ctx;
-  int rc = fte_setup(ctx, h->S, skel_ints, n_ints, skel_reals, n_reals, cams, n_cams, meas, w, n_frames,
-                     shutter_delay, Ts, qinv, sd_mode, intermode, X, tau, op.redesc_a, op.redesc_b, op.redesc_c, flags, &h->own);
-  if (rc) {
-    if (h->own) (void)acs_dev_free(h->own);
-    delete h;
-    return rc;
-  }
-  const FteDims& d = h->S.d;
-  h->R = world;
-  h->rank = rank;
-  h->lam0 = op.lambda0;
-  h->o = FteOptsDev{op.max_iters, op.ftol, op.xtol, op.gtol};
-  // chain length 2^k: smallest k >= 1 with R 2^k >= nblk - 1
-  h->klev = 1;
-  while ((int64_t)world * (1 << h->klev) < d.nblk - 1) h->klev++;
-  h->span = 1 << h->klev;
-  h->a0 = rank * h->span;
-  h->bend = h->a0 + h->span;
-  const int N = d.N, M = d.M;
-  auto clampi = [](int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); };
-  h->own_lo = 3 * h->a0;                    // owned terms: lowest row in [own_lo, own_hi)
-  h->own_hi = rank == world - 1 ? INT_MAX / 2 : 3 * h->bend;  // the last rank owns the tail
-  h->k_lo = clampi(h->own_lo, 0, N);        // frames to linearise
-  h->k_hi = clampi(h->own_hi, 0, N);
-  h->f_lo = clampi(3 * h->a0, 0, M);        // rows to assemble (chain incl. its right end)
-  h->f_hi = clampi(3 * h->bend + 3, 0, M);
-  h->c_lo = clampi(h->own_lo, 0, N);        // cost blocks: frames [lo, hi) and stencils up to hi
-  h->c_hi = clampi(h->own_hi + 1, 0, N);
-  h->out_lo = clampi(h->a0, 0, d.nblk);     // step rows this rank publishes
-  h->out_hi = clampi(rank == world - 1 ? h->bend + 1 : h->bend, 0, d.nblk);
-  h->Lo = dist_layout(d, world);
-  // reduced system arrays
-  FteDims& dr = h->dr;
-  dr = d;
-  dr.nblk = world + 1;
-  dr.M = 1;
-  dr.N = 0;
-  dr.nlev = 0;
-  for (int s = 1; s < dr.nblk; s <<= 1) dr.nlev++;
-  const size_t nb = dr.nblk, BP = d.BP, GR = d.GR;
-  size_t off = 0;
-  auto take = [&](size_t cnt) {
-    size_t o = off;
-    off += ((cnt * sizeof(double) + 255) / 256) * 256 / sizeof(double);
-    return o;
-  };
-  const size_t oD = take(nb * BP * BP), oE = take(nb * BP * BP), oG = take(nb * BP * GR),
-               oW = take(nb * BP * (2 * BP + GR)), oT = take(nb * GR * GR), odc = take(nb * BP),
-               oE2 = take(nb * BP * BP), odL = take(nb * BP * (BP + GR)), odR = take(nb * BP * (BP + GR)),
-               op_ = take((size_t)CR_NCHUNK * (16 * 16 + 16 + 32 * 32)), ogm = take(4);
-  void* p = nullptr;
-  if (acs_dev_malloc(&p, off * sizeof(double)) != hipSuccess) {
-    (void)acs_dev_free(h->own);
-    delete h;
-    return acs_fail(ctx, ACS_E_NOMEM, "fte_dist: reduced-system allocation failed");
-  }
-  h->own_red = p;
-  double* a = (double*)p;
-  h->r = h->S.b;
-  h->r.Dc = a + oD;
-  h->r.Ec = a + oE;
-  h->r.GBc = a + oG;
-  h->r.Wc = a + oW;
-  h->r.Tau = a + oT;
-  h->r.Ec2 = a + oE2;
-  h->r.dL = a + odL;
-  h->r.dR = a + odR;
-  h->r.dcv = a + odc;
-  h->r.part = a + op_;
-  h->r.gmaxp = a + ogm;
-  FteState st0;
-  std::memset(&st0, 0, sizeof(st0));
-  st0.lam = op.lambda0;
-  st0.relin = 1;
-  st0.first = 1;
-  ACS_HIP(ctx, hipMemcpyAsync(h->S.b.st, &st0, sizeof(st0), hipMemcpyHostToDevice, ctx->stream));
-  ACS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  bool snap_ok = acs_host_malloc((void**)&h->snap, sizeof(int32_t) * ACS_DIST_RING, hipHostMallocDefault) == hipSuccess;
-  for (auto& e : h->snap_ev)
-    if (snap_ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) {
-      e = nullptr;
-      snap_ok = false;
-    }
-  if (!snap_ok) {
-    acs_fte_dist_destroy(h);
-    return acs_fail(ctx, ACS_E_HIP, "fte_dist: pinned status ring allocation failed");
-  }
-  if (payload_sizes) {
-    payload_sizes[0] = (int64_t)(h->Lo.n1 + h->Lo.n3);
-    payload_sizes[1] = (int64_t)h->Lo.n2;
-    payload_sizes[2] = (int64_t)h->Lo.n3;
-  }
-  *out = h;
-  return ACS_OK;
-}
-
-// A solve restarted on the same handle: X / tau from the caller (host or, with
-// ACS_DEVICE_PTRS, device pointers; tau NULL = zeros), the LM state of acs_fte_dist_create
-// (first round pending, lambda0), the back-substitution tickets and granules zeroed. The
-// arena, the reduced-system arrays, the status ring and the captured round graphs are kept:
-// no allocation, so a timed multi-GPU solve can reuse one handle per rank.
-int acs_fte_dist_reset(acs_fte_dist* h, const double* X, const double* tau, uint32_t flags) {
-  ACS_DEVICE_GUARD(h ? h->ctx : nullptr);
-  ACS_CHECK(h ? h->ctx : nullptr, h && X, "fte_dist_reset: null handle or X");
-  acs_ctx* ctx = h->ctx;
-  const FteDims& d = h->S.d;
-  FteBuffers& b = h->S.b;
-  hipStream_t s = ctx->stream;
-  // rounds of the previous solve still queued finish first (their snapshots are then stale)
-  ACS_HIP(ctx, hipStreamSynchronize(s));
-  const double* Xs = X;
-  const double* ts = tau;
-  if (!(flags & ACS_DEVICE_PTRS)) {
-    ACS_HIP(ctx, hipMemcpyAsync(b.X, X, sizeof(double) * d.M * d.P, hipMemcpyHostToDevice, s));
-    if (tau) ACS_HIP(ctx, hipMemcpyAsync(b.tau, tau, sizeof(double) * d.NT, hipMemcpyHostToDevice, s));
-    Xs = b.X;
-    ts = tau ? b.tau : nullptr;
-  }
-  const int n = d.nblk, BP = d.BP, GR = d.GR;
-  const size_t MP = (size_t)d.M * d.P;
-  const size_t ngd = (size_t)n * BP * 2 + 64;
-  const size_t nI = std::max(std::max(std::max(MP, (size_t)n + 1), ngd), (size_t)std::max(d.NT, GR));
-  hipLaunchKernelGGL(k_fte_init_state, dim3(acs_grid((int64_t)nI, 256)), dim3(256), 0, s, b.X, Xs, MP, b.tau, ts,
-                     d.NT, b.bad, b.dtau, GR, b.bk, n + 1, b.gdcv, ngd);
-  hipLaunchKernelGGL(k_fte_state_reset, dim3(1), dim3(64), 0, s, b.st, h->lam0);
-  ACS_HIP(ctx, hipGetLastError());
-  h->rounds = 0;
-  return ACS_OK;
-}
-
-int acs_fte_dist_destroy(acs_fte_dist* h) {
-  ACS_DEVICE_GUARD(h ? h->ctx : nullptr);
-  if (!h) return ACS_OK;
-  (void)hipStreamSynchronize(h->ctx->stream);
-  for (auto& c : h->g)
-    if (c.exec) (void)hipGraphExecDestroy(c.exec);
-  for (auto& e : h->snap_ev)
-    if (e) (void)hipEventDestroy(e);
-  if (h->snap) (void)acs_host_free(h->snap);
-  if (h->own) (void)acs_dev_free(h->own);
-  if (h->own_red) (void)acs_dev_free(h->own_red);
-  delete h;
-  return ACS_OK;
-}
-
-static int dist_phase1_body(acs_fte_dist* h, double* p1);
-
-// payload of the starting state: the reduced system at X0 and the owned terms' cost
-int acs_fte_dist_init(acs_fte_dist* h, double* payload) {
-  ACS_DEVICE_GUARD(h ? h->ctx : nullptr);
-  acs_ctx* ctx = h->ctx;
-  const FteDims& d = h->S.d;
-  FteBuffers& b = h->S.b;
-  hipStream_t s = ctx->stream;
-  double* p3 = payload + h->Lo.n1;
-  if (h->c_hi > h->c_lo)
-    hipLaunchKernelGGL(k_fte_cost, dim3(h->c_hi - h->c_lo), dim3(64), 0, s, d, b.I, b.Rl, b.cams, b.meas, b.w, b.X,
-                       b.tau, b.qinv, b.st, 0, h->c_lo, h->own_lo, h->own_hi, b.Fm, b.Fq);
-  hipLaunchKernelGGL(k_dist_cost_pack, dim3(1), dim3(256), 0, s, b.st, 0, d.N, h->c_lo, h->c_hi, h->c_lo, h->c_hi,
-                     (const double*)b.Fm, (const double*)b.Fq, 0, 0, (const double*)nullptr, p3);
-  // the linearisation of the starting state (copy 0); later ones are speculative (phase 3)
-  if (h->a0 < d.nblk && h->k_hi > h->k_lo)
-    fte_launch_lin(d, s, b, 1, h->k_lo, h->k_hi - h->k_lo, 0, (double*)nullptr, (const double*)nullptr);
-  ACS_HIP(ctx, hipGetLastError());
-  return dist_phase1_body(h, payload);
-}
-
-static int dist_phase1_body(acs_fte_dist* h, double* p1) {
-  ACS_DEVICE_GUARD(h ? h->ctx : nullptr);
-  acs_ctx* ctx = h->ctx;
-  const FteDims& d = h->S.d;
-  FteBuffers& b = h->S.b;
-  hipStream_t s = ctx->stream;
-  ACS_HIP(ctx, hipMemsetAsync(p1, 0, sizeof(double) * h->Lo.n1, s));
-  if (h->a0 < d.nblk) {
-    // the linearisation of X[cur] is there already (init, or the speculative one of phase 3)
-    // the chain's rows assembled in LDS and its super-blocks built in one pass (the banded
-    // rows never reach HBM), as the single-GPU solve; the ends' raw diagonals / gradients
-    // go to Adiag / gb (row layout) for the payload
-    const int top = std::min(h->bend, d.nblk - 1);
-    if (d.var) {
-      // per-frame delays: eliminated per frame in the row assembly (damped with the LM
-      // lambda), the rows' gradients before that kept for the payload, then the build
-      hipLaunchKernelGGL(k_fte_assemble, dim3(h->f_hi - h->f_lo), dim3(256), 0, s, d, b.X, b.tau, b.qinv, b.st, 0,
-                         h->f_lo, h->own_lo, h->own_hi, b.Hloc, b.gloc, b.Ab, b.gb, b.Bt, b.gmaxp, b.Adiag, 1, b.graw,
-                         b.gmaxt);
-      cr_launch_build(d, s, top - h->a0 + 1, b.st, b.Ab, b.gb, b.Bt, b.Dc, b.Ec, b.GBc, h->a0, h->a0, h->bend, b.Adiag);
-    } else {
-      cr_launch_assemble_build(d, h->S.n_cu, s, b, h->a0, top - h->a0 + 1, h->own_lo, h->own_hi, h->a0, h->bend,
-                               b.Adiag, b.graw);
-    }
-    const double* Efin = dist_local_cr(h);
-    hipLaunchKernelGGL(k_cr_tau_partial, dim3(CR_NCHUNK), dim3(512), 0, s, d, b.st, b.Hloc, b.gloc, b.Tau, b.part,
-                       h->k_lo, h->k_hi, h->a0 + 1, std::min(h->bend, d.nblk), 1,
-                       (const double*)b.Tc);
-    hipLaunchKernelGGL(k_dist_pack, dim3(32, 2), dim3(256), 0, s, d, b.st, h->Lo, h->rank, h->a0, h->bend, b.Dc, Efin,
-                       b.GBc, b.Adiag, b.graw, p1);
-    hipLaunchKernelGGL(k_dist_pack_small, dim3(1), dim3(256), 0, s, d, b.st, h->Lo, h->rank, h->a0, h->bend, b.part,
-                       b.gmaxp, p1, d.var ? (const double*)b.gmaxt : (const double*)nullptr);
-  }
-  ACS_HIP(ctx, hipGetLastError());
-  return ACS_OK;
-}
-
-// ACS_DIST_BACK_LEVELS=1: the rank chain's back substitution as one k_cr_back launch per level
-// plus k_cr_trial (the round-5 form, kept for A/B timing); default: k_cr_back_chain
-static bool dist_back_levels() {
-  static const bool v = [] {
-    const char* e = std::getenv("ACS_DIST_BACK_LEVELS");
-    return e && e[0] == '1';
-  }();
-  return v;
-}
-
-static int dist_phase2_body(acs_fte_dist* h, const double* p1) {
-  ACS_DEVICE_GUARD(h ? h->ctx : nullptr);
-  acs_ctx* ctx = h->ctx;
-  const FteDims& d = h->S.d;
-  const FteDims& dr = h->dr;
-  FteBuffers& b = h->S.b;
-  FteBuffers& r = h->r;
-  hipStream_t s = ctx->stream;
-  // reduced system (identical on every rank)
-  hipLaunchKernelGGL(k_red_build, dim3(dr.nblk), dim3(256), 0, s, d, b.st, h->Lo, h->R, h->span, p1, r.Dc, r.Ec,
-                     r.GBc, r.gmaxp);
-  const int rb = dr.nblk - 1;
-  CrPending pend;
-  cr_reduce(dr, s, b.st, r, 0, dr.nblk, rb, dr.nlev, b.bad, false, &pend, false);
-  cr_launch_top(dr, s, dr.nlev, 0, dr.nblk, b.st, r, b.bad, pend);
-  hipLaunchKernelGGL(k_cr_tau_partial, dim3(CR_NCHUNK), dim3(512), 0, s, dr, b.st, r.Hloc, r.gloc, r.Tau, r.part, 0,
-                     0, 0, dr.nblk, 0, (const double*)nullptr);
-  const int nE = d.Cg * d.Cg + d.Cg + d.GR * d.GR;
-  hipLaunchKernelGGL(k_red_part, dim3(1), dim3(256), 0, s, nE, h->Lo, b.st, p1, r.part);
-  hipLaunchKernelGGL(k_cr_top, dim3(1), dim3(1024), 0, s, dr, b.st, (const double*)r.Wc, r.part, r.gmaxp, b.tau, r.dcv,
-                     b.dtau, b.bad);
-  hipLaunchKernelGGL(k_dist_gtol, dim3(1), dim3(64), 0, s, b.st, h->o);
-  for (int lv = dr.nlev - 1; lv >= 0; --lv) {
-    const int st = 1 << lv;
-    const int ne = (dr.nblk - st + 2 * st - 1) / (2 * st);
-    hipLaunchKernelGGL(k_cr_back, dim3(ne), dim3(1024), 0, s, dr, st, 0, rb, b.st, r.Wc, b.dtau, r.dcv);
-  }
-  // this chain: ends from the reduced solve, interior by back substitution, then the trial
-  // rows of the whole chain (its end blocks are shared: both neighbours step them alike) and
-  // the replicated delays; the norm partials of the owned blocks go to phase 3's payload
-  if (h->a0 < d.nblk && !d.var && !dist_back_levels()) {
-    hipLaunchKernelGGL(k_dist_scatter, dim3(1), dim3(128), 0, s, d, b.st, h->rank, h->a0, h->bend, r.dcv, b.dcv);
-    // the chain's back substitution and trial rows in one launch (k_cr_back_chain)
-    const int iend = std::min(h->bend, d.nblk);
-    int nint = 0;
-    for (int lv = h->klev - 1; lv >= 0; --lv) {
-      const int sv = 1 << lv;
-      nint += std::max(0, (iend - h->a0 - sv + 2 * sv - 1) / (2 * sv));
-    }
-    const int nwork = (h->bend < d.nblk ? 2 : 1) + nint;
-    const int nth_back = (8 * d.BP + 63) / 64 * 64;
-#define CR_BACK_CHAIN(nb, grb)                                                                                  \
-  hipLaunchKernelGGL((k_cr_back_chain<nb, grb>), dim3(nwork), dim3(nth_back), 0, s, d, h->a0, h->bend, h->klev,  \
-                     h->rank == 0 ? 1 : 0, (const FteState*)b.st, (const double*)b.Wc, (const double*)b.dtau, b.dcv, \
-                     b.bk, b.gdcv, b.bad, b.X, b.tau, b.normp)
-#define CR_BACK_CHAIN_G(nb) \
-  if (d.GR <= 16)           \
-    CR_BACK_CHAIN(nb, 1);   \
-  else                      \
-    CR_BACK_CHAIN(nb, 2)
-    switch (d.BP >> 4) {
-      case 1: CR_BACK_CHAIN_G(1); break;
-      case 2: CR_BACK_CHAIN_G(2); break;
-      case 3: CR_BACK_CHAIN_G(3); break;
-      case 4: CR_BACK_CHAIN_G(4); break;
-      case 5: CR_BACK_CHAIN_G(5); break;
-      default: CR_BACK_CHAIN_G(6); break;
-    }
-#undef CR_BACK_CHAIN_G
-#undef CR_BACK_CHAIN
-  } else if (h->a0 < d.nblk) {
-    hipLaunchKernelGGL(k_dist_scatter, dim3(1), dim3(128), 0, s, d, b.st, h->rank, h->a0, h->bend, r.dcv, b.dcv);
-    for (int lv = h->klev - 1; lv >= 0; --lv) {
-      const int st = 1 << lv;
-      int ne = 0;
-      for (int i = h->a0 + st; i < std::min(h->bend, d.nblk); i += 2 * st) ++ne;
-      if (ne)
-        hipLaunchKernelGGL(k_cr_back, dim3(ne), dim3(1024), 0, s, d, st, h->a0, h->bend, b.st, b.Wc, b.dtau, b.dcv);
-    }
-    const int top = std::min(h->bend, d.nblk - 1);
-    hipLaunchKernelGGL(k_cr_trial, dim3(top - h->a0 + 1), dim3(256), 0, s, d, b.st, (const double*)b.dcv, b.dtau,
-                       b.Hloc, b.gloc, b.X, b.tau, b.normp, 1, h->a0, h->rank == 0 ? 1 : 0, h->k_lo, h->k_hi,
-                       b.normt);
-  } else {
-    // a rank past the last block still steps the replicated delays
-    hipLaunchKernelGGL(k_cr_trial, dim3(1), dim3(256), 0, s, d, b.st, (const double*)b.dcv, b.dtau, b.Hloc, b.gloc,
-                       b.X, b.tau, b.normp, 0, d.nblk, h->rank == 0 ? 1 : 0);
-  }
-  ACS_HIP(ctx, hipGetLastError());
-  return ACS_OK;
-}
-
-static int dist_phase3_body(acs_fte_dist* h, double* p3) {
-  ACS_DEVICE_GUARD(h ? h->ctx : nullptr);
-  acs_ctx* ctx = h->ctx;
-  const FteDims& d = h->S.d;
-  FteBuffers& b = h->S.b;
-  hipStream_t s = ctx->stream;
-  // speculative linearisation of the trial rows: its measurement terms (owned frames
-  // [k_lo, k_hi)) and model stencils (owned: k - 1 in [own_lo, own_hi), so frames up to k_hi
-  // inclusive; the one extra frame's own terms are not counted) are the trial cost, and an
-  // accepted step needs no new linearisation in phase 1
-  const int l_hi = std::min(h->k_hi + 1, d.N);
-  if (h->a0 < d.nblk && l_hi > h->k_lo)
-    fte_launch_lin(d, s, b, 0, h->k_lo, l_hi - h->k_lo, 1, b.Fq, b.qinv);
-  const int q0 = std::max(h->k_lo + 1, 1), q1 = l_hi;
-  const int t_hi = std::min(h->bend, d.nblk - 1) + 1;
-  hipLaunchKernelGGL(k_dist_cost_pack, dim3(1), dim3(256), 0, s, b.st, 1, d.N, h->k_lo, h->k_hi, q0,
-                     std::max(q0, q1), (const double*)b.Floc, (const double*)b.Fq, h->out_lo, h->out_hi, b.normp, p3,
-                     d.var ? h->a0 : 0, d.var ? t_hi : 0, (const double*)b.normt);
-  ACS_HIP(ctx, hipGetLastError());
-  return ACS_OK;
-}
-
-// one LM step: decide on the pending step (summed cost in `in`), solve the summed reduced
-// system of `in`, step the chain, the new trial cost -> `out`, then the reduced system at the
-// trial state (or, after a rejection, at the unchanged state) -> `out`
-int acs_fte_dist_round(acs_fte_dist* h, const double* in, double* out) {
-  ACS_DEVICE_GUARD(h ? h->ctx : nullptr);
-  ACS_CHECK(h ? h->ctx : nullptr, h && in && out && in != out, "fte_dist_round: two distinct payload buffers");
-  acs_ctx* ctx = h->ctx;
-  FteBuffers& b = h->S.b;
-  hipStream_t s = ctx->stream;
-  const size_t n1 = h->Lo.n1;
-  int rc = dist_run_captured(h, in, out, [&] {
-    hipLaunchKernelGGL(k_dist_decide, dim3(1), dim3(64), 0, s, b.st, h->o, in + n1);
-    int r2 = dist_phase2_body(h, in);
-    if (r2) return r2;
-    if ((r2 = dist_phase3_body(h, out + n1))) return r2;
-    hipLaunchKernelGGL(k_dist_spec, dim3(1), dim3(64), 0, s, b.st, 1);
-    if ((r2 = dist_phase1_body(h, out))) return r2;
-    hipLaunchKernelGGL(k_dist_spec, dim3(1), dim3(64), 0, s, b.st, 0);
-    ACS_HIP(ctx, hipGetLastError());
-    return ACS_OK;
-  });
-  if (rc) return rc;
-  const int slot = (int)(h->rounds % ACS_DIST_RING);
-  ACS_HIP(ctx, hipMemcpyAsync(h->snap + slot, &b.st->status, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  ACS_HIP(ctx, hipEventRecord(h->snap_ev[slot], s));
-  h->rounds++;
-  return ACS_OK;
-}
-
-// LM status after round r (waits for that round only)
-int acs_fte_dist_poll(acs_fte_dist* h, int64_t round, int32_t* status) {
-  ACS_DEVICE_GUARD(h ? h->ctx : nullptr);
-  ACS_CHECK(h ? h->ctx : nullptr, h && status && round >= 0 && round < h->rounds && round >= h->rounds - ACS_DIST_RING,
-            "fte_dist_poll: round %lld not among the last %d enqueued", (long long)round, ACS_DIST_RING);
-  const int slot = (int)(round % ACS_DIST_RING);
-  ACS_HIP(h->ctx, hipEventSynchronize(h->snap_ev[slot]));
-  *status = h->snap[slot];
-  return ACS_OK;
-}
-
-int acs_fte_dist_gather(acs_fte_dist* h, double* p2) {
-  ACS_DEVICE_GUARD(h ? h->ctx : nullptr);
-  acs_ctx* ctx = h->ctx;
-  const FteDims& d = h->S.d;
-  FteBuffers& b = h->S.b;
-  hipStream_t s = ctx->stream;
-  ACS_HIP(ctx, hipMemsetAsync(p2, 0, sizeof(double) * h->Lo.n2, s));
-  if (h->out_hi > h->out_lo)
-    hipLaunchKernelGGL(k_dist_x_out, dim3(64), dim3(256), 0, s, d, b.st, h->out_lo, h->out_hi, (const double*)b.X, p2,
-                       (const double*)b.tau, h->k_lo, h->k_hi);
-  ACS_HIP(ctx, hipGetLastError());
-  return ACS_OK;
-}
-
-int acs_fte_dist_scatter(acs_fte_dist* h, const double* p2) {
-  ACS_DEVICE_GUARD(h ? h->ctx : nullptr);
-  acs_ctx* ctx = h->ctx;
-  const FteDims& d = h->S.d;
-  FteBuffers& b = h->S.b;
-  hipLaunchKernelGGL(k_dist_x_in, dim3(64), dim3(256), 0, ctx->stream, d, b.st, p2, b.X, b.tau);
-  ACS_HIP(ctx, hipGetLastError());
-  return ACS_OK;
-}
-
-int acs_fte_dist_result(acs_fte_dist* h, double* X, double* tau, acs_fte_report* report, uint32_t flags) {
-  ACS_DEVICE_GUARD(h ? h->ctx : nullptr);
-  acs_ctx* ctx = h->ctx;
-  const FteDims& d = h->S.d;
-  FteBuffers& b = h->S.b;
-  hipStream_t s = ctx->stream;
-  FteState hs;
-  ACS_HIP(ctx, hipMemcpyAsync(&hs, b.st, sizeof(hs), hipMemcpyDeviceToHost, s));
-  ACS_HIP(ctx, hipStreamSynchronize(s));
-  const hipMemcpyKind kout = (flags & ACS_DEVICE_PTRS) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-  if (X) ACS_HIP(ctx, hipMemcpyAsync(X, b.X + (size_t)hs.cur * d.M * d.P, sizeof(double) * d.M * d.P, kout, s));
-  if (tau) ACS_HIP(ctx, hipMemcpyAsync(tau, b.tau + (size_t)hs.cur * d.NT, sizeof(double) * d.NT, kout, s));
-  int nbad = 0;
-  ACS_HIP(ctx, hipMemcpyAsync(&nbad, b.bad, sizeof(int), hipMemcpyDeviceToHost, s));
-  ACS_HIP(ctx, hipStreamSynchronize(s));
-  if (report) {
-    report->status = hs.status == 0 ? ACS_STATUS_MAXITER : hs.status;
-    report->iters = hs.iters;
-    report->n_accepted = hs.nacc;
-    report->n_bad_pivots = nbad;
-    report->cost_before = hs.F0;
-    report->cost_after = hs.F;
-    report->cost_meas = hs.Fmeas;
-    report->cost_model = hs.Fmodel;
-    report->grad_max = hs.gmax;
-    report->lambda_final = hs.lam;
-  }
-  return ACS_OK;
-}
-
 }  // extern "C"

@@ -511,11 +511,11 @@ extern "C" int acs_fte_covariance(acs_ctx* ctx, const int32_t* skel_ints, int64_
             "acs_fte_covariance: shutter_delay_mode 'variable' is not supported (the per-frame delays are "
             "eliminated inside the block build); use 'const' or no shutter delay");
   ACS_CHECK(ctx, !shutter_delay || tau, "acs_fte_covariance: shutter_delay needs tau");
+  const FteProblem pb{skel_ints, n_ints, skel_reals, n_reals, cams, n_cams, meas, w, n_frames, shutter_delay, Ts, qinv,
+                      sd_mode, intermode, X, tau, flags};
   FteSetup S;
   int rc;
-  if ((rc = fte_setup(ctx, S, skel_ints, n_ints, skel_reals, n_reals, cams, n_cams, meas, w, n_frames, shutter_delay,
-                      Ts, qinv, sd_mode, intermode, X, tau, 3.0, 10.0, 20.0, flags)))
-    return rc;
+  if ((rc = fte_setup(ctx, S, pb))) return rc;
   const FteDims& d = S.d;
   FteBuffers& b = S.b;
   hipStream_t s = ctx->stream;
@@ -562,12 +562,9 @@ extern "C" int acs_fte_covariance(acs_ctx* ctx, const int32_t* skel_ints, int64_
                     : nullptr;
   if (!dcx || (cov_tau && !dct) || (cov_marker && !dcm)) return ACS_E_NOMEM;
   // the linearisation and the undamped blocks, D stored whole (acs_fte_debug_blocks' route)
-  FteState st0;
-  std::memset(&st0, 0, sizeof(st0));
-  st0.relin = 1;
-  ACS_HIP(ctx, hipMemcpyAsync(b.st, &st0, sizeof(st0), hipMemcpyHostToDevice, s));
-  fte_launch_lin(d, s, b, 1, 0, d.N, 0, (double*)nullptr, (const double*)nullptr);
-  cr_launch_assemble_build(d, S.n_cu, s, b, 0, -1, 0, INT_MAX, -1, -1, nullptr, nullptr, 1);
+  if ((rc = fte_upload_state(ctx, S, 0.0))) return rc;
+  fte_launch_lin(d, s, b, 1, 0, d.N);
+  cr_launch_assemble_build(d, S.n_cu, s, b, 1);
   if (hasg) hipLaunchKernelGGL(k_cov_frame_sums, dim3(CR_NCHUNK), dim3(256), 0, s, d, b.Tc, c.partA);
   hipLaunchKernelGGL(k_cov_prep, dim3(n), dim3(256), 0, s, d, b.tau, c);
   const size_t lds2 = sizeof(double) * 2 * (size_t)BP * (BP + 1);

@@ -14,13 +14,17 @@ python -c "from acinoset_amd import build; build.build(verbose=False)"
 B=acinoset_amd/csrc/build
 F="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -I include -Wno-unused-result"
 case "${1:-ekf}" in
-  ekf) /opt/rocm/bin/hipcc $F -DEKF_PROFILE -c acinoset_amd/csrc/ekf.hip -o $B/ekf_prof.o
-       objs="$B/ctx.o $B/ekf_prof.o $B/fk.o $B/fte.o $B/sba.o $B/sba_ext.o $B/tri.o $B/pipeline.o";;
-  fte) /opt/rocm/bin/hipcc $F -DFTE_PROFILE ${FTE_PROF_DEFS:-} -c acinoset_amd/csrc/fte.hip -o $B/fte_prof.o
-       objs="$B/ctx.o $B/ekf.o $B/fk.o $B/fte_prof.o $B/sba.o $B/sba_ext.o $B/tri.o $B/pipeline.o";;
-  ftevar) /opt/rocm/bin/hipcc $F ${FTE_PROF_DEFS:-} -c acinoset_amd/csrc/fte.hip -o $B/fte_var.o
-       objs="$B/ctx.o $B/ekf.o $B/fk.o $B/fte_var.o $B/sba.o $B/sba_ext.o $B/tri.o $B/pipeline.o";;
+  ekf) src=ekf; alt=ekf_prof; defs="-DEKF_PROFILE";;
+  fte) src=fte; alt=fte_prof; defs="-DFTE_PROFILE ${FTE_PROF_DEFS:-}";;
+  ftevar) src=fte; alt=fte_var; defs="${FTE_PROF_DEFS:-}";;
   *) echo "usage: $0 ekf|fte|ftevar"; exit 2;;
 esac
+/opt/rocm/bin/hipcc $F $defs -c acinoset_amd/csrc/$src.hip -o $B/$alt.o
+# one object per csrc/*.hip, as the normal build links them, with the one above in place of its own
+objs=""
+for f in acinoset_amd/csrc/*.hip; do
+  n=$(basename "$f" .hip)
+  if [ "$n" = "$src" ]; then objs="$objs $B/$alt.o"; else objs="$objs $B/$n.o"; fi
+done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $objs -o $B/${OUT:-libprof.so}
 echo "built $B/${OUT:-libprof.so} (${1:-ekf})"

@@ -1,9 +1,6 @@
 """Per-phase wall-clock split of k_cr_level (block 0 of each launch), from a library built
-with -DFTE_PROFILE:
-  B=acinoset_amd/csrc/build; hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -I include -DFTE_PROFILE \
-     -c acinoset_amd/csrc/fte.hip -o $B/fte_prof.o && hipcc --offload-arch=gfx950 -shared -fPIC \
-     $B/{ctx,ekf,fk,sba,sba_ext,tri,pipeline}.o $B/fte_prof.o -o $B/libprof.so
-then python tools/prof_fte_phases.py [frames]."""
+with -DFTE_PROFILE (tools/build_prof.sh fte -> acinoset_amd/csrc/build/libprof.so), then
+python tools/prof_fte_phases.py [frames]."""
 import ctypes as C
 import os
 import sys
