@@ -45,7 +45,7 @@ SYMBOLS = (
     'acs_fte_dist_create', 'acs_fte_dist_init', 'acs_fte_dist_round', 'acs_fte_dist_poll',
     'acs_fte_dist_gather', 'acs_fte_dist_scatter', 'acs_fte_dist_result',
     'acs_fte_dist_destroy', 'acs_fte_dist_reset', 'acs_alloc_events', 'acs_ekf_singular_count',
-    'acs_fte_debug_blocks', 'acs_fte_debug_plan',
+    'acs_fte_debug_blocks', 'acs_fte_debug_plan', 'acs_ekf_debug_plan',
     'acs_sba_ext_dist_create', 'acs_sba_ext_dist_init', 'acs_sba_ext_dist_round', 'acs_sba_ext_dist_poll',
     'acs_sba_ext_dist_result', 'acs_sba_ext_dist_destroy', 'acs_ekf_run',
     'acs_sba_ekf_pipeline', 'acs_fte_covariance', 'acs_sba_set_lm_layout', 'acs_sba_lm_layout',
@@ -220,6 +220,7 @@ def _declare(lib):
         'acs_fte_debug_blocks': (C.c_int, [_P, _P, i64, _P, i64, _P, i32, _P, _P, i32, i32, dbl, _P, i32, i32, _P, _P,
                                            dbl, i32, _P, C.POINTER(i64), u32]),
         'acs_fte_debug_plan': (C.c_int, [_P, i32, i32, i32, i32, i32, i32, C.POINTER(i32), C.POINTER(i32), i32]),
+        'acs_ekf_debug_plan': (C.c_int, [i32, i32, i32, i32, i32, i32, i32, C.POINTER(i32)]),
         'acs_triangulate_pairs': (C.c_int, [_P, _P, i32, _P, _P, _P, _P, i64, _P, u32]),
         'acs_triangulate_dense': (C.c_int, [_P, _P, i32, _P, _P, i64, _P, _P, u32]),
         'acs_sba_ext_default_opts': (None, [C.POINTER(SbaExtOpts)]),
@@ -281,6 +282,31 @@ def fte_debug_plan(n_frames, P, n_cams, shutter_delay=True, sd_mode='const', n_c
     plan['levels'] = [(int(lv[4 * l]), int(lv[4 * l + 1]), int(lv[4 * l + 2]), bool(lv[4 * l + 3]))
                       for l in range(plan['nlev'])]
     return plan
+
+
+EKF_FILTERS = ('k_ekf_filter', 'k_ekf_filter_w1')
+EKF_GAINS = ('none', 'k_ekf_gain_w', 'k_ekf_gain', 'k_ekf_gain_t<3>', 'k_ekf_gain_t<4>', 'k_ekf_gain_t<5>',
+             'k_ekf_gain_t<6>')
+EKF_SMOOTHERS = ('k_ekf_smooth', 'k_ekf_smooth_xs<18,8>', 'k_ekf_smooth_xs<87,2>', 'k_ekf_smooth_x')
+
+
+def ekf_debug_plan(P, n_cams, L, n_frames, covariances=False, n_joints=None, n_nodes=None):
+    """acs_ekf_debug_plan (test hook, no GPU): the kernels acs_ekf_run picks for a table of P
+    parameters, L markers, n_joints joints and n_nodes nodes (P may be a SkeletonTable, which
+    gives all four; the counts default to one joint and L nodes, the smallest table), n_cams
+    cameras and n_frames frames, with (covariances) or without P_smooth. Returns a dict: filter,
+    gains, smoother (kernel names, EKF_FILTERS / EKF_GAINS / EKF_SMOOTHERS), waves, npad, lds."""
+    if hasattr(P, 'ints'):
+        P, L, n_joints, n_nodes = P.P, P.L, P.n_joints, P.n_nodes
+    n_joints = 1 if n_joints is None else n_joints
+    n_nodes = L if n_nodes is None else n_nodes
+    plan = (C.c_int32 * 6)()
+    rc = load_library().acs_ekf_debug_plan(int(P), int(n_joints), int(n_nodes), int(n_cams), int(L), int(n_frames),
+                                           int(bool(covariances)), plan)
+    if rc != 0:
+        raise ValueError(f'acs_ekf_debug_plan: shape refused (rc {rc})')
+    return dict(filter=EKF_FILTERS[plan[0]], waves=int(plan[1]), gains=EKF_GAINS[plan[2]],
+                smoother=EKF_SMOOTHERS[plan[3]], npad=int(plan[4]), lds=int(plan[5]))
 
 
 def alloc_events():

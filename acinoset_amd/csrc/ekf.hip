@@ -2400,6 +2400,76 @@ __global__ __launch_bounds__(((8 * NN + 63) / 64) * 64) void k_ekf_smooth_xs(Ekf
 
 unsigned long long* g_ekf_prof = nullptr;
 
+// The shape fields of EkfDims for a table of P parameters, J joints, K nodes and L markers
+// seen by C cameras over N frames (blob sizes: acs_skeleton in the header).
+static void ekf_shape(EkfDims& d, int P, int J, int K, int C, int L, int N) {
+  d.N = N;
+  d.C = C;
+  d.L = L;
+  d.P = P;
+  d.J = J;
+  d.n = 3 * P;
+  d.npad = ((d.n + 15) / 16) * 16;
+  d.Ppad = ((P + 15) / 16) * 16;
+  d.m = 2 * C * L;
+  d.mpad = ((d.m + 15) / 16) * 16;
+  d.n_ints = FK_HDR + 9 * J + 4 * K + L + 4 * P + K * P;
+  d.n_reals = 3 * K;
+}
+
+// What acs_ekf_enqueue launches for a shape: every choice it makes by size, in one place
+// (acs_ekf_debug_plan returns it to the tests).
+struct EkfPlan {
+  int filter;    // 0: k_ekf_filter, 1: k_ekf_filter_w1
+  int waves;     // waves per sequence of the filter
+  int gains;     // 0: none, 1: k_ekf_gain_w, 2: k_ekf_gain, 3..6: k_ekf_gain_t<NB> + k_ekf_gain_piv
+  int smoother;  // 0: k_ekf_smooth, 1: k_ekf_smooth_xs<18, 8>, 2: k_ekf_smooth_xs<87, 2>, 3: k_ekf_smooth_x
+  int gp;        // gains per workgroup of k_ekf_gain_t (1 / 2)
+  size_t lds;    // dynamic LDS bytes of the filter
+};
+enum { EKF_PLAN_OK = 0, EKF_PLAN_LDS, EKF_PLAN_NPAD };
+
+// Pure host function of the shape (and of ACS_EKF_WG, ACS_EKF_W1_WAVES, ACS_EKF_GAIN_GP, read
+// once per process). Returns EKF_PLAN_LDS when the 8-wave filter's LDS passes 160 KB (pl.lds
+// holds the bytes), EKF_PLAN_NPAD when the parallel gains cannot take the state.
+static int ekf_plan(const EkfDims& d, bool with_p_smooth, EkfPlan& pl) {
+  const int P = d.P, n = d.n;
+  const size_t U = std::max(ekf_wg_fk_doubles(P, d.J, d.L, d.Ppad), ekf_wg_la_doubles(d.npad, d.Ppad));
+  const size_t lds_f = sizeof(double) * ((size_t)d.npad * (d.npad + 1) + U + d.npad +
+                                          (size_t)d.C * ACS_CAM_STRIDE + d.n_reals + (d.n_ints + 1) / 2 + 1);
+  const size_t lds_w1 = sizeof(double) * ekf_w1_lds(d);
+  // ACS_EKF_WG=1 keeps the 8-wave kernel for every model (A/B measurements, tools/ekf_drift.py)
+  static const bool force_wg = acs_env_int("ACS_EKF_WG", 0) == 1;
+  const bool w1 = P == EKF_W1_P && lds_w1 <= 64 * 1024 && !force_wg;
+  // ACS_EKF_W1_WAVES: waves per sequence of the small-state filter (4 by default; 1 for A/B)
+  static const int w1_waves = acs_env_int("ACS_EKF_W1_WAVES", 4) == 1 ? 1 : 4;
+  // two gains per workgroup: one 144 KB workgroup per CU (a workgroup of >= 54 KB of LDS never
+  // shares a CU, tools/probe/lds_occ_probe.hip: the 72 KB one-gain form ran one gain per CU)
+  // one gain per workgroup, two workgroups per CU: 4.09 ms for the bench's 64 x 499 gains;
+  // two gains per 768-thread workgroup (lockstep barriers) 4.31 ms (ACS_EKF_GAIN_GP=2, A/B)
+  static const int gp = acs_env_int("ACS_EKF_GAIN_GP", 1) == 2 ? 2 : 1;
+  pl.filter = w1 ? 1 : 0;
+  pl.waves = w1 ? w1_waves : EKF_WAVES;
+  pl.lds = w1 ? lds_w1 : lds_f;
+  pl.gp = gp;
+  pl.gains = 0;
+  pl.smoother = 0;
+  if (!w1 && lds_f > 160 * 1024) return EKF_PLAN_LDS;
+  if (with_p_smooth) return EKF_PLAN_OK;  // the sequential smoother forms its own gains
+  // gains in parallel over (sequence, frame), then the state recursion per sequence
+  if (d.npad > 96) return EKF_PLAN_NPAD;
+  if (d.N >= 2) {
+    if (n == 3 * EKF_W1_P)  // small states: one wave per gain
+      pl.gains = 1;
+    else if (d.npad >= 48)  // tiled gains, then the pivoted path for any P_pred that is not positive definite
+      pl.gains = std::min(d.npad >> 4, 6);
+    else
+      pl.gains = 2;
+  }
+  pl.smoother = n == 3 * EKF_W1_P ? 1 : n == 87 ? 2 : 3;  // 87: default
+  return EKF_PLAN_OK;
+}
+
 // Filter + smoother on device buffers (common.hpp). hdr = the skeleton table header. x_pred
 // may be null (workspace then), P_est null = workspace, P_smooth null = no covariance
 // smoother (gains in parallel, then the state recursion). Sets io.outliers (device,
@@ -2413,18 +2483,7 @@ int acs_ekf_enqueue(acs_ctx* ctx, int n_ints, int n_reals, const int* hdr, int n
   ACS_CHECK(ctx, n_seq >= 1 && n_frames >= 1 && n_cams >= 1 && n_cams <= 64 && fps > 0 && eps > 0,
             "ekf: n_seq=%d n_frames=%d n_cams=%d", n_seq, n_frames, n_cams);
   EkfDims d;
-  d.N = n_frames;
-  d.C = n_cams;
-  d.L = L;
-  d.P = P;
-  d.J = Jn;
-  d.n = 3 * P;
-  d.npad = ((d.n + 15) / 16) * 16;
-  d.Ppad = ((P + 15) / 16) * 16;
-  d.m = 2 * n_cams * L;
-  d.mpad = ((d.m + 15) / 16) * 16;
-  d.n_ints = n_ints;
-  d.n_reals = n_reals;
+  ekf_shape(d, P, Jn, K, n_cams, L, n_frames);
   d.S = n_seq;
   d.sT = 1.0 / fps;
   d.thresh = thresh;
@@ -2457,34 +2516,28 @@ int acs_ekf_enqueue(acs_ctx* ctx, int n_ints, int n_reals, const int* hdr, int n
   int* dbad = ctx->ekf_bad;
   io.bad = dbad;
   ACS_HIP(ctx, hipMemsetAsync(dbad, 0, sizeof(int), s));
-  const size_t U = std::max(ekf_wg_fk_doubles(P, Jn, L, d.Ppad), ekf_wg_la_doubles(d.npad, d.Ppad));
-  const size_t lds_f = sizeof(double) * ((size_t)d.npad * (d.npad + 1) + U + d.npad +
-                                          (size_t)n_cams * ACS_CAM_STRIDE + n_reals + (n_ints + 1) / 2 + 1);
-  const size_t lds_w1 = sizeof(double) * ekf_w1_lds(d);
-  // ACS_EKF_WG=1 keeps the 8-wave kernel for every model (A/B measurements, tools/ekf_drift.py)
-  static const bool force_wg = acs_env_int("ACS_EKF_WG", 0) == 1;
-  const bool w1 = P == EKF_W1_P && lds_w1 <= 64 * 1024 && !force_wg;
-  // ACS_EKF_W1_WAVES: waves per sequence of the small-state filter (4 by default; 1 for A/B)
-  static const int w1_waves = acs_env_int("ACS_EKF_W1_WAVES", 4) == 1 ? 1 : 4;
-  ACS_CHECK(ctx, w1 || lds_f <= 160 * 1024, "ekf: P = %d needs %zu bytes of LDS", P, lds_f);
+  EkfPlan pl;
+  const int prc = ekf_plan(d, dPs != nullptr, pl);
+  ACS_CHECK(ctx, prc != EKF_PLAN_LDS, "ekf: P = %d needs %zu bytes of LDS", P, pl.lds);
+  ACS_CHECK(ctx, prc != EKF_PLAN_NPAD, "ekf: n = %d", d.n);
   ACS_CHECK(ctx, ref_numerics >= 0 && ref_numerics <= ACS_EKF_ANALYTIC_H, "ekf: numerics mode %d", ref_numerics);
   // analytic H: the FkShared of one FK lives in the batched-FK region of the LDS union
   // small states (the head model): k_ekf_filter_w1
 #define EKF_W1_NW(f32, ah, nw)                                                                                     \
-  hipLaunchKernelGGL((k_ekf_filter_w1<f32, ah, EKF_W1_P, nw>), dim3(n_seq), dim3(64 * nw), lds_w1, s, d, io.I, \
+  hipLaunchKernelGGL((k_ekf_filter_w1<f32, ah, EKF_W1_P, nw>), dim3(n_seq), dim3(64 * nw), pl.lds, s, d, io.I, \
                      io.R, io.cams, io.meas, io.lik, io.rstd, io.Q, io.P0, io.s0, dxp, dxe, dPp, dPe, dout, dbad,         \
                      g_ekf_prof)
 #define EKF_W1(f32, ah)          \
-  if (w1_waves == 4)             \
+  if (pl.waves == 4)             \
     EKF_W1_NW(f32, ah, 4);       \
   else                           \
     EKF_W1_NW(f32, ah, 1)
-#define EKF_FILTER(f32, ah)                                                                                         \
-  if (w1)                                                                                                           \
-    EKF_W1(f32, ah);                                                                                                \
-  else                                                                                                              \
-    hipLaunchKernelGGL((k_ekf_filter<f32, ah>), dim3(n_seq), dim3(512), lds_f, s, d, io.I, io.R, io.cams, io.meas, \
-                       io.lik, io.rstd, io.Q, io.P0, io.s0, dxp, dxe, dPp, dPe, scr, dout, dbad, g_ekf_prof)
+#define EKF_FILTER(f32, ah)                                                                                          \
+  if (pl.filter == 1)                                                                                                \
+    EKF_W1(f32, ah);                                                                                                 \
+  else                                                                                                               \
+    hipLaunchKernelGGL((k_ekf_filter<f32, ah>), dim3(n_seq), dim3(64 * EKF_WAVES), pl.lds, s, d, io.I, io.R, io.cams, \
+                       io.meas, io.lik, io.rstd, io.Q, io.P0, io.s0, dxp, dxe, dPp, dPe, scr, dout, dbad, g_ekf_prof)
   if (ref_numerics == ACS_EKF_ANALYTIC_H)
     EKF_FILTER(false, true);
   else if (ref_numerics)
@@ -2493,54 +2546,45 @@ int acs_ekf_enqueue(acs_ctx* ctx, int n_ints, int n_reals, const int* hdr, int n
     EKF_FILTER(false, false);
 #undef EKF_FILTER
   ACS_HIP(ctx, hipGetLastError());
-  const size_t lds_s = sizeof(double) * ((size_t)d.npad * (d.npad + 1) + 512 + d.npad);
-  if (dPs) {
-    hipLaunchKernelGGL(k_ekf_smooth, dim3(n_seq), dim3(256), lds_s, s, d, dxp, dxe, dPp, dPe, dxs, dPs, scr, dbad, 1);
-  } else {
-    // gains in parallel over (sequence, frame), then the state recursion per sequence
-    ACS_CHECK(ctx, d.npad <= 96, "ekf: n = %d", d.n);
-    if (n_frames >= 2 && n == 3 * EKF_W1_P) {  // small states: one wave per gain
-      const size_t ng = (size_t)n_seq * (n_frames - 1);
-      hipLaunchKernelGGL((k_ekf_gain_w<3 * EKF_W1_P, EKF_GAIN_W>), dim3((unsigned)((ng + EKF_GAIN_W - 1) / EKF_GAIN_W)),
-                         dim3(64 * EKF_GAIN_W), 0, s, d, (const double*)dPe, dPp, dbad);
-    } else if (n_frames >= 2 && d.npad >= 48) {
-      // tiled gains, then the pivoted path for any P_pred that is not positive definite
-      const unsigned ng = (unsigned)((size_t)n_seq * (n_frames - 1));
-      int* dflag = (int*)(scr + std::max(scr_f, scr_s)) + 16 * (size_t)n_seq + 16;
-  // two gains per workgroup: one 144 KB workgroup per CU (a workgroup of >= 54 KB of LDS never
-  // shares a CU, tools/probe/lds_occ_probe.hip: the 72 KB one-gain form ran one gain per CU)
-  // one gain per workgroup, two workgroups per CU: 4.09 ms for the bench's 64 x 499 gains;
-  // two gains per 768-thread workgroup (lockstep barriers) 4.31 ms (ACS_EKF_GAIN_GP=2, A/B)
-  static const int gp = acs_env_int("ACS_EKF_GAIN_GP", 1) == 2 ? 2 : 1;
-#define EKF_GAIN_T(NB)                                                                                          \
-  if (gp == 1)                                                                                                  \
-    hipLaunchKernelGGL((k_ekf_gain_t<NB, 1>), dim3(ng), dim3(64 * NB), 0, s, d, (const double*)dPe, dPp, dflag, \
-                       (int)ng);                                                                                \
-  else                                                                                                          \
-    hipLaunchKernelGGL((k_ekf_gain_t<NB, 2>), dim3((ng + 1) / 2), dim3(128 * NB), 0, s, d, (const double*)dPe,  \
-                       dPp, dflag, (int)ng)
-      switch (d.npad >> 4) {
-        case 3: EKF_GAIN_T(3); break;
-        case 4: EKF_GAIN_T(4); break;
-        case 5: EKF_GAIN_T(5); break;
-        default: EKF_GAIN_T(6); break;
-      }
-#undef EKF_GAIN_T
-      const size_t lds_p = sizeof(double) * ((size_t)n * (2 * n + 1) + n) + sizeof(int) * n;
-      hipLaunchKernelGGL(k_ekf_gain_piv, dim3(ng), dim3(256), lds_p, s, d, (const double*)dPe, dPp,
-                         (const int*)dflag, dbad);
-      ACS_HIP(ctx, hipGetLastError());
-    } else if (n_frames >= 2) {
-      const size_t lds_g = sizeof(double) * ((size_t)d.npad * (d.npad + 1) + 512);
-      hipLaunchKernelGGL(k_ekf_gain, dim3((unsigned)((size_t)n_seq * (n_frames - 1))), dim3(256), lds_g, s, d,
-                         (const double*)dPe, dPp, dbad);
-      ACS_HIP(ctx, hipGetLastError());
+  const size_t ng = (size_t)n_seq * (n_frames - 1);  // gains, over (sequence, frame)
+  if (pl.gains == 1) {
+    hipLaunchKernelGGL((k_ekf_gain_w<3 * EKF_W1_P, EKF_GAIN_W>), dim3((unsigned)((ng + EKF_GAIN_W - 1) / EKF_GAIN_W)),
+                       dim3(64 * EKF_GAIN_W), 0, s, d, (const double*)dPe, dPp, dbad);
+  } else if (pl.gains == 2) {
+    const size_t lds_g = sizeof(double) * ((size_t)d.npad * (d.npad + 1) + 512);
+    hipLaunchKernelGGL(k_ekf_gain, dim3((unsigned)ng), dim3(256), lds_g, s, d, (const double*)dPe, dPp, dbad);
+    ACS_HIP(ctx, hipGetLastError());
+  } else if (pl.gains >= 3) {
+    int* dflag = (int*)(scr + std::max(scr_f, scr_s)) + 16 * (size_t)n_seq + 16;
+#define EKF_GAIN_T(NB)                                                                                            \
+  if (pl.gp == 1)                                                                                                 \
+    hipLaunchKernelGGL((k_ekf_gain_t<NB, 1>), dim3((unsigned)ng), dim3(64 * NB), 0, s, d, (const double*)dPe,     \
+                       dPp, dflag, (int)ng);                                                                      \
+  else                                                                                                            \
+    hipLaunchKernelGGL((k_ekf_gain_t<NB, 2>), dim3((unsigned)((ng + 1) / 2)), dim3(128 * NB), 0, s, d,            \
+                       (const double*)dPe, dPp, dflag, (int)ng)
+    switch (pl.gains) {
+      case 3: EKF_GAIN_T(3); break;
+      case 4: EKF_GAIN_T(4); break;
+      case 5: EKF_GAIN_T(5); break;
+      default: EKF_GAIN_T(6); break;
     }
-    if (n == 3 * EKF_W1_P)
-      EKF_SMOOTH_XS(3 * EKF_W1_P, EKF_SX_D);
-    else if (n == 87)  // default
-      EKF_SMOOTH_XS(87, 2);
-    else
+#undef EKF_GAIN_T
+    const size_t lds_p = sizeof(double) * ((size_t)n * (2 * n + 1) + n) + sizeof(int) * n;
+    hipLaunchKernelGGL(k_ekf_gain_piv, dim3((unsigned)ng), dim3(256), lds_p, s, d, (const double*)dPe, dPp,
+                       (const int*)dflag, dbad);
+    ACS_HIP(ctx, hipGetLastError());
+  }
+  switch (pl.smoother) {
+    case 0: {
+      const size_t lds_s = sizeof(double) * ((size_t)d.npad * (d.npad + 1) + 512 + d.npad);
+      hipLaunchKernelGGL(k_ekf_smooth, dim3(n_seq), dim3(256), lds_s, s, d, dxp, dxe, dPp, dPe, dxs, dPs, scr, dbad,
+                         1);
+      break;
+    }
+    case 1: EKF_SMOOTH_XS(3 * EKF_W1_P, EKF_SX_D); break;
+    case 2: EKF_SMOOTH_XS(87, 2); break;  // default
+    default:
       hipLaunchKernelGGL(k_ekf_smooth_x, dim3(n_seq), dim3(256), 0, s, d, (const double*)dxp, (const double*)dxe,
                          (const double*)dPp, dxs);
   }
@@ -2563,6 +2607,25 @@ void acs_ekf_gain_trace(unsigned long long* out) {
   (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_gain_trace), sizeof(g_gain_trace));
 }
 #endif
+
+int acs_ekf_debug_plan(int32_t P, int32_t n_joints, int32_t n_nodes, int32_t n_cams, int32_t L, int32_t n_frames,
+                       int32_t with_p_smooth, int32_t* plan) {
+  // the shapes acs_ekf_run and acs_ekf_enqueue accept
+  if (!plan || P < 3 || P > FK_MAXP || n_joints < 1 || n_joints > FK_MAXJ || n_nodes > FK_MAXN || L < 1 ||
+      L > n_nodes || n_cams < 1 || n_cams > 64 || n_frames < 1)
+    return ACS_E_INVALID;
+  EkfDims d;
+  ekf_shape(d, P, n_joints, n_nodes, n_cams, L, n_frames);
+  EkfPlan pl;
+  if (ekf_plan(d, with_p_smooth != 0, pl) != EKF_PLAN_OK) return ACS_E_INVALID;
+  plan[0] = pl.filter;
+  plan[1] = pl.waves;
+  plan[2] = pl.gains;
+  plan[3] = pl.smoother;
+  plan[4] = d.npad;
+  plan[5] = (int32_t)pl.lds;
+  return ACS_OK;
+}
 
 int acs_ekf_run(acs_ctx* ctx, const int32_t* skel_ints, int64_t n_ints, const double* skel_reals, int64_t n_reals,
                 const double* cams, int32_t n_cams, const double* meas, const double* likelihood, int32_t n_seq,

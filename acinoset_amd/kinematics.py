@@ -219,8 +219,13 @@ INT_HDR = 8
 
 def build_table(mode: str) -> SkeletonTable:
     joints, nodes = _tree(mode)
-    params = _POSE[mode]
-    markers = _MARKERS[mode]
+    return table_from_tree(mode, joints, nodes, _POSE[mode], _MARKERS[mode])
+
+
+def table_from_tree(name: str, joints: Sequence[Joint], nodes: Sequence[Node], params: Sequence[str],
+                    markers: Sequence[str]) -> SkeletonTable:
+    """The device table of any tree: `joints` (parents by index), `nodes` (bases by name, frames
+    by joint index; one of them named 'head'), the pose parameters and the output markers."""
     pidx = {p: i for i, p in enumerate(params)}
     nidx = {n.name: i for i, n in enumerate(nodes)}
     P, L = len(params), len(markers)
@@ -249,24 +254,24 @@ def build_table(mode: str) -> SkeletonTable:
 
     deriv = np.zeros((K, P), np.int32)
     pk = np.zeros((P, 4), np.int32)
-    for p, name in enumerate(params):
-        if name in ('x_0', 'y_0', 'z_0'):
-            pk[p] = (PK_TRANS, 'xyz'.index(name[0]), 0, 0)
+    for p, pname in enumerate(params):
+        if pname in ('x_0', 'y_0', 'z_0'):
+            pk[p] = (PK_TRANS, 'xyz'.index(pname[0]), 0, 0)
             for k, n in enumerate(nodes):
                 deriv[k, p] = 0 if n.base == 'WORLD' else 1
-        elif name in ('x_l', 'y_l', 'z_l'):
-            pk[p] = (PK_WORLD, 'xyz'.index(name[0]), 0, 0)
+        elif pname in ('x_l', 'y_l', 'z_l'):
+            pk[p] = (PK_WORLD, 'xyz'.index(pname[0]), 0, 0)
             for k, n in enumerate(nodes):
                 deriv[k, p] = 1 if n.base == 'WORLD' else 0
-        elif name == 'l_1':
+        elif pname == 'l_1':
             owner = [k for k, n in enumerate(nodes) if n.offset_param == 'l_1']
             assert len(owner) == 1
             pk[p] = (PK_LEN, owner[0], 0, 0)
             for k in range(K):
                 deriv[k, p] = 1 if owner[0] in chain_of[k] else 0
         else:
-            hit = [(j, r) for j, jt in enumerate(joints) for r, (_, pn) in enumerate(jt.seq) if pn == name]
-            assert len(hit) == 1, name
+            hit = [(j, r) for j, jt in enumerate(joints) for r, (_, pn) in enumerate(jt.seq) if pn == pname]
+            assert len(hit) == 1, pname
             j, r = hit[0]
             pk[p] = (PK_ROT, j, r, 0)
             for k in range(K):
@@ -290,7 +295,7 @@ def build_table(mode: str) -> SkeletonTable:
     ints += pk.ravel().tolist()
     ints += deriv.ravel().tolist()
     reals = np.array([c for n in nodes for c in n.offset], np.float64)
-    return SkeletonTable(mode, P, L, J, K, np.asarray(ints, np.int32), reals, list(markers), list(params))
+    return SkeletonTable(name, P, L, J, K, np.asarray(ints, np.int32), reals, list(markers), list(params))
 
 
 def fk_numpy(mode: str, x: np.ndarray, shift: Optional[np.ndarray] = None,

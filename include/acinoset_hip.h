@@ -542,6 +542,18 @@ int acs_ekf_run(acs_ctx* ctx, const int32_t* skel_ints, int64_t n_ints, const do
  * synchronises anyway (host arrays, or an outlier report) already fails on them; a
  * device-pointer call without outliers does not check, and this reads the count afterwards. */
 int acs_ekf_singular_count(acs_ctx* ctx, int32_t* count);
+/* Test hook, host only (no context, no device memory, no launch): the kernels acs_ekf_run
+ * picks for a skeleton table of P parameters, n_joints joints, n_nodes nodes and L markers
+ * seen by n_cams cameras over n_frames frames, with or without P_smooth, from the function the
+ * run itself dispatches with (the table's joint and node counts size its place in the filter's
+ * LDS). plan[6] = {filter (0: k_ekf_filter, 1: k_ekf_filter_w1), waves of the filter,
+ * gains (0: none, 1: k_ekf_gain_w, 2: k_ekf_gain, 3..6: k_ekf_gain_t<NB> + k_ekf_gain_piv),
+ * smoother (0: k_ekf_smooth, 1: k_ekf_smooth_xs<18,8>, 2: k_ekf_smooth_xs<87,2>,
+ * 3: k_ekf_smooth_x), npad (3P padded to 16), filter LDS bytes}. ACS_E_INVALID where the run
+ * refuses the shape: P outside 3..32, n_cams outside 1..64, a table out of range, or a filter
+ * that needs more than 160 KB of LDS. */
+int acs_ekf_debug_plan(int32_t P, int32_t n_joints, int32_t n_nodes, int32_t n_cams, int32_t L,
+                       int32_t n_frames, int32_t with_p_smooth, int32_t* plan);
 
 /* ---- configs[4]: SBA + EKF fused on one observation tensor ------------------------------
  * core.sba (src/core/sba.py:27-70) and core.ekf (src/core/ekf.py:26-298) of the same
