@@ -52,7 +52,7 @@ SYMBOLS = (
     'acs_project_standard', 'acs_sba_lm_layout_flags',
     'acs_sba_points_covariance', 'acs_sba_points_dense_covariance',
     'acs_sba_ext_cov_default_opts', 'acs_sba_extrinsics_covariance',
-    'acs_sba_boards', 'acs_sba_boards_chunk',
+    'acs_sba_boards', 'acs_sba_boards_chunk', 'acs_sba_boards_covariance',
 )
 
 
@@ -170,6 +170,18 @@ class SbaExtCovReport(C.Structure):
         return d
 
 
+class SbaBoardsCovReport(C.Structure):
+    _fields_ = [('status', C.c_int32), ('reserved', C.c_int32), ('n_boards', C.c_int64), ('n_ok', C.c_int64),
+                ('n_noobs', C.c_int64), ('n_degenerate', C.c_int64), ('dof', C.c_int64), ('min_pivot', C.c_double),
+                ('sigma_hat_px', C.c_double), ('rot_sd_max', C.c_double), ('trans_sd_max', C.c_double),
+                ('board_rot_sd_max', C.c_double), ('board_trans_sd_max', C.c_double)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != 'reserved'}
+        d['status_name'] = 'degenerate' if self.status else 'ok'
+        return d
+
+
 # must equal ACS_ABI_VERSION in include/acinoset_hip.h (checked when the library loads)
 ABI_VERSION = 5
 _lib = None
@@ -253,6 +265,8 @@ def _declare(lib):
         'acs_sba_boards': (C.c_int, [_P, _P, i32, _P, i32, _P, _P, i32, _P, C.POINTER(SbaExtOpts), _P, _P,
                                      C.POINTER(SbaExtReport), u32]),
         'acs_sba_boards_chunk': (i32, [i32]),
+        'acs_sba_boards_covariance': (C.c_int, [_P, _P, i32, _P, i32, _P, _P, i32, _P, C.POINTER(SbaExtCovOpts), _P, _P,
+                                                _P, C.POINTER(SbaBoardsCovReport), u32]),
     }
     for name, (res, args) in sig.items():
         if not hasattr(lib, name):
@@ -668,6 +682,47 @@ class Context:
         self.check(self.lib.acs_sba_boards(self.h, v(cams_p), n_cams, v(obj_p), n_corners, v(uv_p), v(mask_p), n_boards,
                                            v(poses_p), C.byref(opts), v(resid_before_p), v(resid_after_p),
                                            C.byref(rep), ACS_DEVICE_PTRS), 'acs_sba_boards')
+        return rep.as_dict()
+
+    def sba_boards_covariance(self, cams, obj_pts, uv, mask, board_r, board_t, f_scale=1.0, sigma_px=1.0,
+                              gauge='anchor', anchor=0):
+        """acs_sba_boards_covariance at (`cams`, `board_r`, `board_t`) (nothing is solved): the covariance
+        of the camera poses in the chosen gauge and of every board pose. Arrays as `sba_boards`. Returns
+        (cov_cams (6C, 6C), cov_boards (B, 6, 6), board_status (B,) int32, report dict). Rows 6c..6c+5
+        of cov_cams are camera c's (dw, dt): R <- exp([dw]x) R (rad), t <- t + dt (m); a board's block
+        is its (dw_b, dt_b). gauge 'free': inner constraints over the camera parameters
+        (sigma^2 pinv(S)); 'anchor': camera `anchor`'s pose held (its rows and columns are exact
+        zeros). A degenerate problem (report['status'] = 1) returns NaN everywhere; a board that is
+        not OK has a NaN block. `f_scale` is the solve's."""
+        if gauge not in GAUGES:
+            raise ValueError(f"gauge must be 'free' or 'anchor', not {gauge!r}")
+        cams = _c64(cams)
+        obj = _c64(obj_pts).reshape(-1, 3)
+        mask = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
+        n_b, n_c = mask.shape
+        uv = _c64(uv, (n_b, n_c, len(obj), 2))
+        poses = np.concatenate([_c64(board_r, (n_b, 9)), _c64(board_t, (n_b, 3))], 1)
+        o = SbaExtCovOpts(GAUGES[gauge], int(anchor), 0, 0, float(f_scale), float(sigma_px))
+        cov_c = np.empty((6 * len(cams), 6 * len(cams)))
+        cov_b = np.empty((n_b, 6, 6))
+        status = np.empty(n_b, np.int32)
+        rep = SbaBoardsCovReport()
+        self.check(self.lib.acs_sba_boards_covariance(self.h, _ptr(cams), len(cams), _ptr(obj), len(obj), _ptr(uv),
+                                                      _ptr(mask), n_b, _ptr(poses), C.byref(o), _ptr(cov_c),
+                                                      _ptr(cov_b), _ptr(status), C.byref(rep), _std_flag(cams)),
+                   'acs_sba_boards_covariance')
+        return cov_c, cov_b, status, rep.as_dict()
+
+    def sba_boards_covariance_dev(self, cams_p, n_cams, obj_p, n_corners, uv_p, mask_p, n_boards, poses_p, cov_cams_p,
+                                  cov_boards_p=0, status_p=0, f_scale=1.0, sigma_px=1.0, gauge='anchor', anchor=0):
+        """acs_sba_boards_covariance on raw device addresses (ACS_DEVICE_PTRS); returns the report dict."""
+        o = SbaExtCovOpts(GAUGES[gauge], int(anchor), 0, 0, float(f_scale), float(sigma_px))
+        rep = SbaBoardsCovReport()
+        v = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+        self.check(self.lib.acs_sba_boards_covariance(self.h, v(cams_p), n_cams, v(obj_p), n_corners, v(uv_p),
+                                                      v(mask_p), n_boards, v(poses_p), C.byref(o), v(cov_cams_p),
+                                                      v(cov_boards_p), v(status_p), C.byref(rep), ACS_DEVICE_PTRS),
+                   'acs_sba_boards_covariance')
         return rep.as_dict()
 
     def sba_extrinsics_covariance(self, cams, uv, pt_idx, cam_idx, pts, f_scale=1.0, sigma_px=1.0, gauge='anchor',

@@ -34,11 +34,15 @@ def sba_board_points_fisheye(scene_fpath, points_fpaths, out_fpath, manual_point
                              sigma_px=sigma_px)
 
 
-def sba_board_poses_fisheye(scene_fpath, points_fpaths, out_fpath, camera_indices=None):
+def sba_board_poses_fisheye(scene_fpath, points_fpaths, out_fpath, camera_indices=None, covariance=False,
+                            sigma_px=1.0):
     """Extrinsics refined with one rigid pose per board image and the known square length
     (`_sba_board_poses`): the scene JSON at out_fpath and `<out_fpath stem>_boards.json` beside it.
-    Hand-labelled manual points are not part of this solve."""
-    return _sba_board_poses(scene_fpath, points_fpaths, out_fpath, camera_indices)
+    Hand-labelled manual points are not part of this solve. `covariance=True` also writes
+    `<out_fpath stem>_cov.json` and the board pose covariances into `_boards.json`; the scene JSON
+    is the same file either way."""
+    return _sba_board_poses(scene_fpath, points_fpaths, out_fpath, camera_indices, covariance=covariance,
+                            sigma_px=sigma_px)
 
 
 def _gaze_targets(head_pos, nose_pos, r_eye_pos, r=3.0):

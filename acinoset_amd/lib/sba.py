@@ -476,14 +476,22 @@ def prepare_calib_boards_for_bundle_adjustment(img_pts_arr, fnames_arr, board_sh
 
 
 def bundle_adjust_boards_and_extrinsics(uv, mask, obj_pts, board_r, board_t, k_arr, d_arr, r_arr, t_arr, f_scale=1.0,
-                                        **opts):
+                                        covariance=False, sigma_px=1.0, gauge='anchor', anchor=None, **opts):
     """acs_sba_boards: every camera's rotation and translation (intrinsics fixed, fisheye model) and one
     rigid pose per board image refined together on the Cauchy objective of
     bundle_adjust_points_and_extrinsics. The known board geometry fixes the metric scale. uv
     (B, C, nc, 2), mask (B, C), obj_pts (nc, 3), board poses X = board_r p + board_t. Returns (board_r
     (B, 3, 3), board_t (B, 3), r_arr (C, 3, 3), t_arr (C, 3, 1), {'before', 'after', 'report'}); the
     residuals hold the seen views in (board, camera, corner, row) order. opts: max_iters, ftol, xtol,
-    gtol, lambda0."""
+    gtol, lambda0.
+    `covariance=True` adds to the returned dict, evaluated at the returned solution with the same
+    f_scale and the pixel noise `sigma_px` (acs_sba_boards_covariance): `cov_cams` (6C, 6C), camera
+    c's (dw, dt) at rows 6c..6c+5 with R <- exp([dw]x) R (rad) and t <- t + dt (m); `cov_cam_blocks`
+    (C, 6, 6), its diagonal blocks; `cov_boards` (B, 6, 6), every board pose's (dw_b, dt_b) (NaN for
+    a board that is not OK); `cov_status` (B,) and `cov_report` (with 'gauge' and 'anchor'). gauge
+    'anchor' holds the pose of camera `anchor` (default 0) and nothing else: the board fixes the
+    scale; 'free' is the inner-constraint gauge. The poses and residuals are those of the plain
+    call."""
     ctx = _native.default_context()
     n = len(k_arr)
     o = ctx.sba_ext_opts(f_scale=float(f_scale), **opts)
@@ -496,13 +504,28 @@ def bundle_adjust_boards_and_extrinsics(uv, mask, obj_pts, board_r, board_t, k_a
     print(f'\nOptimization took {t1 - t0:.2f} seconds')
     r_out = cams[:, 8:17].reshape(n, 3, 3).copy()
     t_out = cams[:, 17:20].reshape(n, 3, 1).copy()
-    return br, bt, r_out, t_out, dict(before=rb, after=ra, report=rep)
+    res = dict(before=rb, after=ra, report=rep)
+    if covariance:
+        a = 0 if anchor is None else int(anchor)
+        cc, cb, cst, crep = ctx.sba_boards_covariance(cams, obj_pts, uv, mask, br, bt, f_scale=float(f_scale),
+                                                      sigma_px=float(sigma_px), gauge=gauge, anchor=a)
+        crep.update(gauge=gauge, anchor=a if gauge == 'anchor' else None)
+        print(f'GPU SBA board-rig covariance ({gauge}): {crep["status_name"]}, rotation sd <= '
+              f'{crep["rot_sd_max"]:.3e} rad, translation sd <= {crep["trans_sd_max"]:.3e} m; sigma_hat '
+              f'{crep["sigma_hat_px"]:.4f} px (sigma_px {float(sigma_px):g})')
+        blocks = np.stack([cc[6 * c:6 * c + 6, 6 * c:6 * c + 6] for c in range(n)])
+        res.update(cov_cams=cc, cov_cam_blocks=blocks, cov_boards=cb, cov_status=cst, cov_report=crep)
+    return br, bt, r_out, t_out, res
 
 
-def _sba_board_poses(scene_fpath, points_fpaths, out_fpath, camera_indices=None):
+def _sba_board_poses(scene_fpath, points_fpaths, out_fpath, camera_indices=None, covariance=False, sigma_px=1.0):
     """Board corners -> rigid-board SBA (bundle_adjust_boards_and_extrinsics) -> refined scene JSON at
     out_fpath and `<out_fpath stem>_boards.json` beside it: per board image its name, pose (r, t) and
-    view count, and the report. The square length is the points files'. Returns the residual dict."""
+    view count, and the report. The square length is the points files'. Returns the residual dict.
+    `covariance=True` also writes `<out_fpath stem>_cov.json` (save_pose_covariance: camera 0 held,
+    nothing else; camera blocks, sds, centres and centre covariances) and gives each board entry of
+    `_boards.json` its `cov` (6 x 6, (dw_b, dt_b)), `rotation_sd`, `translation_sd` and `status`
+    (NaN written as null). The scene file is the same either way."""
     img_pts_arr, fnames_arr, board_shape, square_len = [], [], None, None
     if camera_indices is None:
         camera_indices = range(len(points_fpaths))
@@ -515,7 +538,9 @@ def _sba_board_poses(scene_fpath, points_fpaths, out_fpath, camera_indices=None)
     print('bundle_adjust_boards_and_extrinsics')
     uv, mask, obj, br, bt, names = prepare_calib_boards_for_bundle_adjustment(img_pts_arr, fnames_arr, board_shape,
                                                                               square_len, k_arr, d_arr, r_arr, t_arr)
-    br, bt, r_arr, t_arr, res = bundle_adjust_boards_and_extrinsics(uv, mask, obj, br, bt, k_arr, d_arr, r_arr, t_arr)
+    kw = dict(covariance=True, sigma_px=sigma_px) if covariance else {}
+    br, bt, r_arr, t_arr, res = bundle_adjust_boards_and_extrinsics(uv, mask, obj, br, bt, k_arr, d_arr, r_arr, t_arr,
+                                                                    **kw)
     print(f"\nBefore: mean: {np.mean(res['before'])}, std: {np.std(res['before'])}")
     print(f"After: mean: {np.mean(res['after'])}, std: {np.std(res['after'])}\n")
     save_scene(out_fpath, k_arr, d_arr, r_arr, t_arr, cam_res)
@@ -524,6 +549,17 @@ def _sba_board_poses(scene_fpath, points_fpaths, out_fpath, camera_indices=None)
                 parameters='per board X = r p + t: board coordinates to world coordinates (m)',
                 boards=[dict(name=fn, r=br[b].tolist(), t=bt[b].tolist(), n_views=int(mask[b].sum()))
                         for b, fn in enumerate(names)], report=rep)
+    if covariance:
+        save_pose_covariance(os.path.splitext(out_fpath)[0] + '_cov.json', res, r_arr, t_arr, sigma_px)
+        names_st = ('ok', 'noobs', 'degenerate')
+
+        def lst(a):  # NaN (a board that is not OK, a degenerate problem) is not JSON: null
+            return [lst(x) for x in a] if np.ndim(a) else (None if np.isnan(a) else float(a))
+        for b, entry in enumerate(data['boards']):
+            blk = res['cov_boards'][b]
+            sd = np.sqrt(blk.diagonal())
+            entry.update(cov=lst(blk), rotation_sd=lst(sd[:3]), translation_sd=lst(sd[3:]),
+                         status=names_st[int(res['cov_status'][b])])
     with open(os.path.splitext(out_fpath)[0] + '_boards.json', 'w') as f:
         json.dump(data, f, indent=2)
     res.update(board_r=br, board_t=bt, names=names, mask=mask, uv=uv, obj_pts=obj)

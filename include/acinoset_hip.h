@@ -493,6 +493,62 @@ int acs_sba_extrinsics_covariance(acs_ctx* ctx, const double* cams, int32_t n_ca
                                   double* cov_cams, double* cov_pts, int32_t* pt_status,
                                   acs_sba_ext_cov_report* report, uint32_t flags);
 
+/* ---- camera and board pose covariances of the rigid-board SBA --------------------------
+ * Evaluated at the cameras and board poses passed in; nothing is solved.
+ * Problem and linearisation: those of acs_sba_boards. Fisheye records, 1 <= n_cams (C) <= 16,
+ * 3 <= n_corners (nc) <= 256, n_boards (B) >= 1, uv (B, C, nc, 2), mask (B, C), board_poses
+ * (B, 12). Left perturbations R <- exp([dw]x) R, t <- t + dt for cameras and boards;
+ * J_cam = J_Y [-[R_c X]x | I], J_pt = J_Y R_c, J_brd = J_pt [-[R_b p_j]x | I]; Triggs weights
+ * wh = max((1 - z) w^2, 0.1 w), w = 1 / (1 + z), z = r^2 / f_scale^2. Per seen view U_bc and
+ * W_bc (6 x 6); per board V_b = sum_views sum wh J_brd^T J_brd. All undamped.
+ * Board status (int32 per board, ACS_COV_*): ACS_COV_NOOBS without a view; ACS_COV_DEGENERATE
+ * when an entry of diag V_b is not > 0, or a pivot of the unpivoted LDL^T of V_b scaled to unit
+ * diagonal fails d > 1e-9 (a NaN fails; a collinear target is an example; the scaling matters
+ * because V_b mixes rad^-2 and m^-2); ACS_COV_OK otherwise (a board with one view of a planar
+ * target is OK). A board that is not OK is left out entirely (its U, W and V terms), so S G = 0
+ * stays exact.
+ * Reduced system: S = sum_OK U_bc - sum_OK W_b V_b^-1 W_b^T (6C x 6C, symmetrised), W_b the
+ * 6C x 6 stack of the board's view blocks.
+ * Gauge generators G (6C x 6), per camera c: rotation theta: dw_c = -R_c theta, dt_c = 0;
+ * translation tau: dw_c = 0, dt_c = -R_c tau (the boards move with dw_b = theta,
+ * dt_b = -[t_b]x theta + tau). S G = 0.
+ * ACS_GAUGE_FREE: with Q = orth(G) and mu = max diag S,
+ *   cov_cc = sigma_px^2 [(S + mu Q Q^T)^-1 - Q Q^T / mu]   (= sigma_px^2 pinv(S)).
+ * ACS_GAUGE_ANCHOR (the default): the pose of camera anchor_cam (a) is held. Cm (6 x 6C) is the
+ * identity on camera a,
+ *   cov_cc = P cov_free P^T,  P = I - G (Cm G)^-1 Cm,
+ * camera a's rows and columns exact zeros. scale_cam is ignored: the board fixes the scale.
+ * Problem status: ACS_EXT_COV_DEGENERATE when, with Ah = S + mu Q Q^T scaled to unit diagonal, a
+ * diagonal entry is not > 0 (a camera seen by no OK board ends here or at the next test), a
+ * pivot of the unpivoted LDL^T of Ah in natural order fails d > 1e-9, or G has rank < 6. Then
+ * every covariance is NaN. min_pivot as in acs_sba_extrinsics_covariance.
+ * n_cams = 1 is decided before S is formed: the camera is pure gauge, so cov_cams is exact
+ * zeros in both gauges, the status is OK, min_pivot is NaN (nothing is factored) and the boards
+ * get sigma_px^2 V_b^-1.
+ * Boards (OK boards; NaN for the others):
+ *   cov_b = sigma_px^2 V_b^-1 + V_b^-1 W_b^T cov_cc W_b V_b^-1   (6 x 6, (dw_b, dt_b), rad and m).
+ * sigma_hat_px^2 = sum w r^2 / dof over the residuals of the OK boards' views,
+ * dof = m - 6 n_ok - (6C - 6) (NaN when dof <= 0): reported, never applied.
+ * cov_cams (6C, 6C); cov_boards (B, 6, 6) and board_status (B) may be NULL; every matrix is
+ * exactly symmetric. Host pointers, or ACS_DEVICE_PTRS for every array. The call waits for the
+ * stream. ACS_E_INVALID before anything is staged: f_scale or sigma_px <= 0, n_cams outside
+ * 1..16, n_corners outside 3..256, n_boards < 1, anchor_cam out of range in the anchor gauge, an
+ * unknown gauge, ACS_CAMS_STANDARD.                                                          */
+typedef struct {
+  int32_t status, reserved;                 /* ACS_EXT_COV_* */
+  int64_t n_boards, n_ok, n_noobs, n_degenerate, dof;
+  double min_pivot, sigma_hat_px;
+  double rot_sd_max, trans_sd_max;              /* cameras (rad, m) */
+  double board_rot_sd_max, board_trans_sd_max;  /* OK boards (rad, m) */
+} acs_sba_boards_cov_report;
+int acs_sba_boards_covariance(acs_ctx* ctx, const double* cams, int32_t n_cams, const double* obj_pts,
+                              int32_t n_corners, const double* uv, const uint8_t* mask,
+                              int32_t n_boards, const double* board_poses,
+                              const acs_sba_ext_cov_opts* opts /* scale_cam ignored */,
+                              double* cov_cams /* 6C x 6C */, double* cov_boards /* B x 6 x 6, may be NULL */,
+                              int32_t* board_status /* may be NULL */, acs_sba_boards_cov_report* report,
+                              uint32_t flags);
+
 /* ---- §8(e): points + extrinsics SBA over ranks -------------------------------------
  * Each rank passes its own points and their observations (point indices local to the
  * rank); cameras are replicated. ONE all-reduce per LM step:
