@@ -66,6 +66,28 @@ struct SbaParams {
   double f_scale, ftol, xtol, gtol;
 };
 
+// Diagnostic build only (tools/probe/lm_timeline_probe.hip defines ACS_LM_STAMPS and includes this
+// file; the library is never built with it): the ROW instances read the shader clock at seven
+// points of the wave's life and lane 0 of the wave stores them. ACS_STAMP_AFTER names the values the
+// program has to hold at that point, so that the stamp stands behind their waits and arithmetic.
+#ifdef ACS_LM_STAMPS
+static unsigned long long* g_lm_stamps = nullptr;  // 8 words per wave, set by acs_sba_lm_stamps (probe)
+#define ACS_STAMP(i) \
+  if constexpr (ROW != 0) tk[i] = __builtin_amdgcn_s_memtime()
+#define ACS_STAMP_AFTER(i, ...)              \
+  if constexpr (ROW != 0) {                  \
+    asm volatile("" ::__VA_ARGS__);          \
+    tk[i] = __builtin_amdgcn_s_memtime();    \
+  }
+#define ACS_STAMPS_PARAM , unsigned long long* __restrict__ stamps
+#define ACS_STAMPS_ARG(p) , p
+#else
+#define ACS_STAMP(i)
+#define ACS_STAMP_AFTER(i, ...)
+#define ACS_STAMPS_PARAM
+#define ACS_STAMPS_ARG(p)
+#endif
+
 // HOIST: each lane keeps its camera record in registers for the whole LM loop instead of
 // re-reading it from LDS in every projection (196 VGPRs: 2 waves per SIMD), chosen for
 // grids of at most 2 waves per SIMD, where nothing else would fill the SIMD anyway.
@@ -75,9 +97,14 @@ struct SbaParams {
 // (profiles/r06/bench_sba_w*_r06h.log): three independent slot chains per lane already keep the
 // VALU issuing, and the 4-wave budget spills.
 // Parameter order: the arguments the first vector loads need come first (observation, mask,
-// point count, point, camera records, then the two counts), so that the kernel-argument preload
-// this file is built with (build.py) hands as many of them as the user SGPRs hold to the wave at
-// launch, with no scalar load and its round trip ahead of the first address.
+// point count, point, camera records, then the two counts), and the solution pointer right
+// behind them, so that the kernel-argument preload this file is built with (build.py) hands all
+// of them to the wave at launch: 14 dwords, as many as the user SGPRs hold, with no scalar load
+// and its round trip ahead of the first address, and none ahead of the final store either (the
+// last thing the slowest wave does; nothing in the wave has touched that line of the
+// kernel-argument segment before, and each graph node has a segment of its own). camid, null
+// in every instance without camera ids and read after the first round only, comes behind the
+// preloaded ones with the LM parameters and the report's pointers.
 // ROW (0, or the number of lane pairs 2..4): the row-broadcast sums of common.hpp in place of the
 // butterfly. G = 16 (one point per DPP row), S = 1, no camera ids, HOIST only: the instance for
 // latency-bound grids, where a wave of 4 points instead of 8 costs nothing (run_lm).
@@ -88,11 +115,16 @@ template <int G, int S, bool CAMID, bool HOIST, int ROW = 0, int MODEL = ACS_MOD
 __global__ __launch_bounds__(256) void k_sba_lm(const double2* __restrict__ uv,
                                                 const uint8_t* __restrict__ mask, int64_t n_pts,
                                                 const double* pts_in, const double* __restrict__ cams,
-                                                int K, int C, const uint8_t* __restrict__ camid,
+                                                int K, int C,
                                                 double* pts,  // may alias pts_in
-                                                SbaParams prm,
+                                                const uint8_t* __restrict__ camid, SbaParams prm,
                                                 double* __restrict__ cost0, double* __restrict__ cost1,
-                                                int* __restrict__ stat) {
+                                                int* __restrict__ stat ACS_STAMPS_PARAM) {
+#ifdef ACS_LM_STAMPS
+  [[maybe_unused]] unsigned long long tk[7] = {0, 0, 0, 0, 0, 0, 0};
+  [[maybe_unused]] const unsigned long long rt0 = __builtin_amdgcn_s_memrealtime();
+#endif
+  ACS_STAMP(0);  // entry
   static_assert(ROW == 0 || (G == 16 && S == 1 && !CAMID && HOIST), "ROW: 16-lane rows, one slot per lane, hoisted records");
   static_assert(MODEL == 0 || (!HOIST && ROW == 0), "standard model: LDS-staged butterfly instances only");
   constexpr int CS = CamRec<MODEL>::stride;
@@ -107,9 +139,11 @@ __global__ __launch_bounds__(256) void k_sba_lm(const double2* __restrict__ uv,
   const int lane = threadIdx.x & (G - 1);
   const int64_t p = ((int64_t)blockIdx.x * bdim + threadIdx.x) / G;
   const bool live = p < n_pts;
-  // every global load is issued before the first wait: the slot's observation, its mask and
-  // camera id, and the point (none depends on another), then the camera records for LDS.
-  // One memory round trip instead of three before the LM loop starts.
+  // the slot's observation, its mask and camera id, and the point (none depends on another),
+  // then the camera records: two round trips, since the compiler ends the block below with a
+  // wait for the mask byte and issues the point's and the records' loads behind it. One round
+  // from clamped indices, with slot < K and the mask as selects, was measured for the HOIST
+  // instances and not kept.
   double2 q[S];
   uint8_t mk[S], cid[S];
 #pragma unroll
@@ -125,6 +159,7 @@ __global__ __launch_bounds__(256) void k_sba_lm(const double2* __restrict__ uv,
       if (CAMID) cid[s] = camid[o];
     }
   }
+  ACS_STAMP_AFTER(1, "v"((int)mk[0]));  // after the first vector wait (the mask byte)
   double x0 = 0.0, x1 = 0.0, x2 = 0.0;
   if (live) {
     x0 = pts_in[3 * p];
@@ -174,8 +209,11 @@ __global__ __launch_bounds__(256) void k_sba_lm(const double2* __restrict__ uv,
   const unsigned long long grp = G == 64 ? ~0ull : (1ull << (G & 63)) - 1ull;
   const bool noobs = ((has >> (threadIdx.x & 63 & ~(G - 1))) & grp) == 0ull;
   const int max_iters = noobs ? 0 : prm.max_iters;
-  const double f2 = prm.f_scale * prm.f_scale;
-  const double if2 = 1.0 / f2;
+  // f_scale is not preloaded: its scalar load is waited for where the value is first used. The
+  // HOIST instances pass it through the null-record statement below, so that this wait and the
+  // f_scale^2, 1 / f_scale^2 chain stand behind the constant set-up that runs under the load
+  // latency, not ahead of it
+  double fs = prm.f_scale;
   if constexpr (HOIST) {
 #pragma unroll
     for (int s = 0; s < S; ++s) {
@@ -196,11 +234,15 @@ __global__ __launch_bounds__(256) void k_sba_lm(const double2* __restrict__ uv,
           "s_mov_b64 exec, %[sv]"
           : "+v"(c[0]), "+v"(c[1]), "+v"(c[2]), "+v"(c[3]), "+v"(c[4]), "+v"(c[5]), "+v"(c[6]), "+v"(c[7]),
             "+v"(c[8]), "+v"(c[9]), "+v"(c[10]), "+v"(c[11]), "+v"(c[12]), "+v"(c[13]), "+v"(c[14]), "+v"(c[15]),
-            "+v"(c[16]), "+v"(c[17]), "+v"(c[18]), "+v"(c[19]), [sv] "=&s"(sv)
+            "+v"(c[16]), "+v"(c[17]), "+v"(c[18]), "+v"(c[19]), [sv] "=&s"(sv), "+s"(fs)
           : [nul] "s"(nul)
           : "scc");
     }
   }
+  const double f2 = fs * fs;
+  const double if2 = 1.0 / f2;
+  // after the last vector wait: the point, the observation and (through the statement above) the record
+  ACS_STAMP_AFTER(2, "v"(x0), "v"(x1), "v"(x2), "v"(ou[0]), "v"(ov[0]), "v"(cr[0][0]), "v"(cr[0][19]));
 
   // One pass over the observations at X: robust cost, Triggs-weighted GN matrix (packed
   // upper 3x3) and IRLS gradient, group-reduced. The trial point of every LM iteration is
@@ -293,6 +335,8 @@ __global__ __launch_bounds__(256) void k_sba_lm(const double2* __restrict__ uv,
   const double F_before = F;
   double lam = 1e-3;
   int status = ACS_STATUS_RUNNING, iters = 0, nfev = 1;
+  ACS_STAMP_AFTER(3, "v"(F), "v"(H[0]), "v"(H[1]), "v"(H[2]), "v"(H[3]), "v"(H[4]), "v"(H[5]), "v"(g[0]), "v"(g[1]),
+                  "v"(g[2]));  // loop entry
   // One pass = solve, stopping tests on the solve, trial linearisation, accept / reject. The
   // pass is straight-line code with two exits (after the solve; at the end): a lone wave pays
   // an issue slot for every exec-mask instruction and branch, so a pass that cannot step (not
@@ -419,18 +463,30 @@ __global__ __launch_bounds__(256) void k_sba_lm(const double2* __restrict__ uv,
     status = fconv ? ACS_STATUS_FTOL : status;
     if (status != ACS_STATUS_RUNNING) break;
   }
-  if (status == ACS_STATUS_RUNNING) {
-    // left at the first exit (g is the one tested there), in the order of its tests
-    const double gmax = fmax(fabs(g[0]), fmax(fabs(g[1]), fabs(g[2])));
-    status = iters >= max_iters ? ACS_STATUS_MAXITER : gmax <= prm.gtol ? ACS_STATUS_GTOL : ACS_STATUS_FTOL;
-  }
+  ACS_STAMP_AFTER(4, "v"(x0), "v"(x1), "v"(x2), "v"(F), "v"(status), "v"(iters));  // loop exit
+  ACS_STAMP(5);                                                                     // before the wait ahead of the store
   if (lane == 0) {
+    ACS_STAMP_AFTER(6, "s"(pts));  // after it
+#ifdef ACS_LM_STAMPS
+    if constexpr (ROW != 0) {
+      if (stamps && threadIdx.x == 0) {  // one wave per block
+        unsigned long long* w = stamps + 8 * (size_t)blockIdx.x;
+        for (int i = 0; i < 7; ++i) w[i] = tk[i];
+        w[7] = __builtin_amdgcn_s_memrealtime() - rt0;
+      }
+    }
+#endif
     pts[3 * p] = x0;
     pts[3 * p + 1] = x1;
     pts[3 * p + 2] = x2;
     // the per-point costs and status feed k_sba_report only: not written (28 B per point)
-    // when no report is asked for
+    // when no report is asked for, and the status of a first-exit leave is not resolved then
     if (stat) {
+      if (status == ACS_STATUS_RUNNING) {
+        // left at the first exit (g is the one tested there), in the order of its tests
+        const double gmax = fmax(fabs(g[0]), fmax(fabs(g[1]), fabs(g[2])));
+        status = iters >= max_iters ? ACS_STATUS_MAXITER : gmax <= prm.gtol ? ACS_STATUS_GTOL : ACS_STATUS_FTOL;
+      }
       cost0[p] = noobs ? 0.0 : F_before;
       cost1[p] = noobs ? 0.0 : F;
       stat[3 * p] = noobs ? ACS_STATUS_NOOBS : status;
@@ -569,14 +625,14 @@ static void launch_lm_t(acs_ctx* ctx, int blocks, int block, const double* cams,
       block = 64;
       blocks = acs_grid(n_pts * G, block);
       hipLaunchKernelGGL((k_sba_lm<G, S, CAMID, true>), dim3(blocks), dim3(block),
-                         sizeof(double) * ACS_CAM_STRIDE * (C + 1), ctx->stream, uv, mask, n_pts, pts_in, cams, K, C, camid,
-                         pts, prm, c0, c1, st);
+                         sizeof(double) * ACS_CAM_STRIDE * (C + 1), ctx->stream, uv, mask, n_pts, pts_in, cams, K, C, pts,
+                         camid, prm, c0, c1, st ACS_STAMPS_ARG(nullptr));
       return;
     }
   }
   hipLaunchKernelGGL((k_sba_lm<G, S, CAMID, false, 0, MODEL>), dim3(blocks), dim3(block),
                      sizeof(double) * CamRec<MODEL>::stride * (C + 1), ctx->stream, uv, mask, n_pts, pts_in, cams, K, C,
-                     camid, pts, prm, c0, c1, st);
+                     pts, camid, prm, c0, c1, st ACS_STAMPS_ARG(nullptr));
 }
 
 template <int S, bool CAMID, int MODEL>
@@ -616,7 +672,7 @@ static void launch_lm_row(acs_ctx* ctx, const double* cams, int C, int K, const 
   const size_t lds = sizeof(double) * ACS_CAM_STRIDE * (C + 1);
 #define ACS_ROW_LAUNCH(r)                                                                                        \
   hipLaunchKernelGGL((k_sba_lm<16, 1, false, true, r>), grid, block, lds, ctx->stream, uv, mask, n_pts, pts_in, cams, \
-                     K, C, (const uint8_t*)nullptr, pts, prm, c0, c1, st)
+                     K, C, pts, (const uint8_t*)nullptr, prm, c0, c1, st ACS_STAMPS_ARG(g_lm_stamps))
   switch ((K + 1) / 2) {
     case 2: ACS_ROW_LAUNCH(2); break;
     case 3: ACS_ROW_LAUNCH(3); break;
