@@ -52,7 +52,7 @@ SYMBOLS = (
     'acs_project_standard', 'acs_sba_lm_layout_flags',
     'acs_sba_points_covariance', 'acs_sba_points_dense_covariance',
     'acs_sba_ext_cov_default_opts', 'acs_sba_extrinsics_covariance',
-    'acs_sba_boards', 'acs_sba_boards_chunk', 'acs_sba_boards_covariance',
+    'acs_sba_boards', 'acs_sba_boards_chunk', 'acs_sba_boards_covariance', 'acs_sba_ext_plan',
 )
 
 
@@ -265,6 +265,7 @@ def _declare(lib):
         'acs_sba_boards': (C.c_int, [_P, _P, i32, _P, i32, _P, _P, i32, _P, C.POINTER(SbaExtOpts), _P, _P,
                                      C.POINTER(SbaExtReport), u32]),
         'acs_sba_boards_chunk': (i32, [i32]),
+        'acs_sba_ext_plan': (C.c_int, [i64, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
         'acs_sba_boards_covariance': (C.c_int, [_P, _P, i32, _P, i32, _P, _P, i32, _P, C.POINTER(SbaExtCovOpts), _P, _P,
                                                 _P, C.POINTER(SbaBoardsCovReport), u32]),
     }
@@ -333,6 +334,17 @@ def sba_boards_chunk(n_cams):
     """acs_sba_boards_chunk: boards per Schur block of acs_sba_boards for n_cams cameras (no GPU
     needed)."""
     return int(load_library().acs_sba_boards_chunk(int(n_cams)))
+
+
+def sba_ext_plan(n_pts, K):
+    """acs_sba_ext_plan (test hook, no GPU needed): what acs_sba_extrinsics selects for n_pts points
+    whose largest observation count is K. Returns a dict: G (lanes per point), chunk (points per
+    Schur block), nchunk (Schur blocks)."""
+    g, chunk, nchunk = C.c_int32(), C.c_int32(), C.c_int32()
+    rc = load_library().acs_sba_ext_plan(int(n_pts), int(K), C.byref(g), C.byref(chunk), C.byref(nchunk))
+    if rc != 0:
+        raise ValueError(f'acs_sba_ext_plan: shape refused (rc {rc})')
+    return dict(G=g.value, chunk=chunk.value, nchunk=nchunk.value)
 
 
 def load_library():

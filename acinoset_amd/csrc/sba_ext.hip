@@ -527,6 +527,17 @@ void acs_sba_ext_default_opts(acs_sba_ext_opts* o) {
   o->lambda0 = 1e-3;
 }
 
+// host only: the dimensions acs_sba_extrinsics launches by (ext_dims, ext_nchunk)
+int acs_sba_ext_plan(int64_t n_pts, int32_t K, int32_t* G, int32_t* chunk, int32_t* nchunk) {
+  if (n_pts < 1 || n_pts >= (int64_t)INT32_MAX || K < 1 || K > EXT_MAXK || !G || !chunk || !nchunk)
+    return ACS_E_INVALID;
+  const ExtDims d = ext_dims(n_pts, K, 1, 1.0);
+  *G = d.G;
+  *chunk = d.chunk;
+  *nchunk = ext_nchunk(d);
+  return ACS_OK;
+}
+
 int acs_sba_extrinsics(acs_ctx* ctx, double* cams, int32_t n_cams, const double* uv, const int32_t* pt_idx,
                        const int32_t* cam_idx, int64_t n_obs, double* pts, int64_t n_pts,
                        const acs_sba_ext_opts* opts, double* resid_before, double* resid_after,
@@ -582,7 +593,9 @@ int acs_sba_extrinsics(acs_ctx* ctx, double* cams, int32_t n_cams, const double*
   }
   ExtState hs;
   std::memset(&hs, 0, sizeof(hs));
-  for (int it = 0; it < op.max_iters + chunk; it += chunk) {
+  // every decision counts an iteration or stops, so max_iters of them end the solve: no replay
+  // beyond them, and none at all for max_iters = 0 (the state comes back as it went in)
+  for (int it = 0; it < op.max_iters; it += chunk) {
     if (use_graph) {
       ACS_HIP(ctx, hipGraphLaunch(exec, s));
     } else {

@@ -394,6 +394,10 @@ int acs_sba_extrinsics(acs_ctx* ctx, double* cams, int32_t n_cams, const double*
                        const int32_t* pt_idx, const int32_t* cam_idx, int64_t n_obs, double* pts,
                        int64_t n_pts, const acs_sba_ext_opts* opts, double* resid_before,
                        double* resid_after, acs_sba_ext_report* report, uint32_t flags);
+/* acs_sba_ext_plan (test hook, host only, no device): what acs_sba_extrinsics selects for n_pts
+ * points whose largest observation count is K: the lane group G of a point (2..64), the points
+ * per Schur block and the number of Schur blocks. ACS_E_INVALID for n_pts < 1 or K outside 1..64. */
+int acs_sba_ext_plan(int64_t n_pts, int32_t K, int32_t* G, int32_t* chunk, int32_t* nchunk);
 
 /* ---- bundle adjustment of extrinsics AND rigid calibration-board poses ------------------
  * One rigid pose per board image instead of one free 3-D point per corner: the known board

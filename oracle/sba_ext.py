@@ -109,7 +109,10 @@ def linearize(X, R, t, K, D, uv, pi, ci, f_scale):
 
 
 def sba_extrinsics(points_2d, points_3d, point_idx, cam_idx, K, D, R0, t0, f_scale=1.0, max_iters=500,
-                   ftol=1e-12, xtol=1e-12, gtol=1e-8, lam0=1e-3):
+                   ftol=1e-12, xtol=1e-12, gtol=1e-8, lam0=1e-3, trace=None):
+    """trace: a list; every iteration appends a dict with the cost F it started from, the trial cost
+    F_new, the step norm dn and state norm xn of the xtol test, gmax and lam as the step was solved
+    with, and whether the step was accepted."""
     uv = np.asarray(points_2d, np.float64)
     X = np.array(points_3d, np.float64).reshape(-1, 3)
     R = np.array(R0, np.float64).reshape(-1, 3, 3)
@@ -165,6 +168,8 @@ def sba_extrinsics(points_2d, points_3d, point_idx, cam_idx, K, D, R0, t0, f_sca
         iters += 1
         dn = np.sqrt((dc ** 2).sum() + (dX ** 2).sum())
         xn = np.sqrt((t ** 2).sum() + (X ** 2).sum())
+        if trace is not None:
+            trace.append(dict(F=F, F_new=Fn, dn=dn, xn=xn, gmax=gmax, lam=lam, accepted=bool(Fn < F)))
         if Fn < F:
             nacc += 1
             fconv = (F - Fn) <= ftol * abs(F)
