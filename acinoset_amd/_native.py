@@ -53,6 +53,7 @@ SYMBOLS = (
     'acs_sba_points_covariance', 'acs_sba_points_dense_covariance',
     'acs_sba_ext_cov_default_opts', 'acs_sba_extrinsics_covariance',
     'acs_sba_boards', 'acs_sba_boards_chunk', 'acs_sba_boards_covariance', 'acs_sba_ext_plan',
+    'acs_sba_boards_points',
 )
 
 
@@ -264,6 +265,8 @@ def _declare(lib):
                                          C.POINTER(SbaExtReport), u32]),
         'acs_sba_boards': (C.c_int, [_P, _P, i32, _P, i32, _P, _P, i32, _P, C.POINTER(SbaExtOpts), _P, _P,
                                      C.POINTER(SbaExtReport), u32]),
+        'acs_sba_boards_points': (C.c_int, [_P, _P, i32, _P, i32, _P, _P, i32, _P, _P, _P, i32, _P,
+                                            C.POINTER(SbaExtOpts), _P, _P, C.POINTER(SbaExtReport), u32]),
         'acs_sba_boards_chunk': (i32, [i32]),
         'acs_sba_ext_plan': (C.c_int, [i64, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
         'acs_sba_boards_covariance': (C.c_int, [_P, _P, i32, _P, i32, _P, _P, i32, _P, C.POINTER(SbaExtCovOpts), _P, _P,
@@ -694,6 +697,50 @@ class Context:
         self.check(self.lib.acs_sba_boards(self.h, v(cams_p), n_cams, v(obj_p), n_corners, v(uv_p), v(mask_p), n_boards,
                                            v(poses_p), C.byref(opts), v(resid_before_p), v(resid_after_p),
                                            C.byref(rep), ACS_DEVICE_PTRS), 'acs_sba_boards')
+        return rep.as_dict()
+
+    def sba_boards_points(self, cams, obj_pts, uv, mask, board_r, board_t, pt_uv, pt_mask, pts0, opts=None,
+                          residuals=True):
+        """acs_sba_boards_points: `sba_boards` with free (hand-labelled) points in the same solve. The
+        board arrays as `sba_boards`; pt_uv (n, C, 2), pt_mask (n, C) the dense observations of the n free
+        points (a camera sees a point at most once) and pts0 (n, 3) their start; n = 0 is the
+        boards-only solve. Returns (cams, board_r, board_t, pts, res_before, res_after, report); the
+        residuals hold the board part as `sba_boards` gives it, then the seen (point, camera) pairs in
+        (point, camera, row) order."""
+        cams = _c64(cams).copy()
+        obj = _c64(obj_pts).reshape(-1, 3)
+        mask = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
+        n_b, n_c = mask.shape
+        uv = _c64(uv, (n_b, n_c, len(obj), 2))
+        poses = np.concatenate([_c64(board_r, (n_b, 9)), _c64(board_t, (n_b, 3))], 1)
+        pts = _c64(pts0).reshape(-1, 3).copy()
+        n = len(pts)
+        pmask = np.ascontiguousarray(np.asarray(pt_mask).reshape(n, n_c) != 0, np.uint8)
+        puv = _c64(pt_uv, (n, n_c, 2))
+        n_res = 2 * (len(obj) * int(mask.sum()) + int(pmask.sum()))
+        rb = np.empty(n_res) if residuals else None
+        ra = np.empty(n_res) if residuals else None
+        rep = SbaExtReport()
+        opts = opts or self.sba_ext_opts()
+        none = lambda a: _ptr(a) if n else None  # noqa: E731
+        self.check(self.lib.acs_sba_boards_points(self.h, _ptr(cams), len(cams), _ptr(obj), len(obj), _ptr(uv),
+                                                  _ptr(mask), n_b, _ptr(poses), none(puv), none(pmask), n, none(pts),
+                                                  C.byref(opts), _ptr(rb), _ptr(ra), C.byref(rep), _std_flag(cams)),
+                   'acs_sba_boards_points')
+        return cams, poses[:, :9].reshape(n_b, 3, 3).copy(), poses[:, 9:].copy(), pts, rb, ra, rep.as_dict()
+
+    def sba_boards_points_dev(self, cams_p, n_cams, obj_p, n_corners, uv_p, mask_p, n_boards, poses_p, pt_uv_p,
+                              pt_mask_p, n_pts, pts_p, opts=None, resid_before_p=0, resid_after_p=0):
+        """acs_sba_boards_points on raw device addresses (ACS_DEVICE_PTRS): cameras, board poses (B, 12)
+        and points (n, 3) are refined in place; the residual arrays hold 2 (nc seen views + seen point
+        observations) doubles; returns the report dict."""
+        rep = SbaExtReport()
+        opts = opts or self.sba_ext_opts()
+        v = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+        self.check(self.lib.acs_sba_boards_points(self.h, v(cams_p), n_cams, v(obj_p), n_corners, v(uv_p), v(mask_p),
+                                                  n_boards, v(poses_p), v(pt_uv_p), v(pt_mask_p), n_pts, v(pts_p),
+                                                  C.byref(opts), v(resid_before_p), v(resid_after_p), C.byref(rep),
+                                                  ACS_DEVICE_PTRS), 'acs_sba_boards_points')
         return rep.as_dict()
 
     def sba_boards_covariance(self, cams, obj_pts, uv, mask, board_r, board_t, f_scale=1.0, sigma_px=1.0,

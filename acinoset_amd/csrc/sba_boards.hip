@@ -619,3 +619,277 @@ int acs_sba_boards(acs_ctx* ctx, double* cams, int32_t n_cams, const double* obj
 }
 
 }  // extern "C"
+
+// =======================================================================================
+// Rigid boards with free (hand-labelled) points in the same solve (acs_sba_boards_points).
+//
+// The problem (the one definition; also in include/acinoset_hip.h and tests/sba_boards_points_ref.py):
+//   everything of acs_sba_boards above, and free points X_p, p = 0..n-1, stored densely:
+//   pt_uv (n, C, 2), pt_mask (n, C): a camera sees a point at most once (slot = camera, K = C in the
+//   terms of sba_ext.hip). The same Cauchy cost and Triggs weights for every residual:
+//   F = F_boards + F_points; U and g_c of a camera sum over its board views and its point
+//   observations. One LM, the spec of oracle/sba_ext.py and of the solve above joined: Marquardt
+//   damping on every diagonal, M_b as above, M_p = (V_p + lam diag V_p + 1e-300 I)^-1 (point_minv),
+//     S = sum U + lam D - sum_b W M_b W^T - sum_p W M_p W^T,
+//     b = -g_c + sum_b W M_b g_b + sum_p W M_p g_p,
+//   db and dX by back-substitution, gmax = max(|g_c|, |g_b|, |g_p|),
+//   |d|^2 = sum dc^2 + sum db^2 + sum dX^2, |x|^2 = sum |t_c|^2 + sum |t_b|^2 + sum |X_p|^2;
+//   accept / reject, the lambda schedule, EXT_LAM_MIN, the stop tests and the status codes as above.
+//   A point without an observation takes no step and contributes nothing (point_minv's rule); a
+//   board without a view behaves as above. The 6-DoF rigid gauge stays free.
+//
+// One iteration: k_brd_linearize, k_ext_linearize; k_brd_schur, k_ext_schur; k_ext_solve;
+// k_brd_back, k_ext_back; k_brd_pose, k_ext_cam; k_brd_cost, k_ext_cost; k_ext_lm. The point side is
+// sba_ext.hip's kernels on the dense slots (ext_launch_*), with ext_dims(n, C, C, f_scale). The two
+// sides meet in flat buffers: part holds the board chunks, then the point chunks; Fp and normp the
+// boards, then the points (k_ext_lm sums B + n entries); one ExtState, dc, Sg, bad, camnorm and
+// camera double buffer. New device code is what the dense form needs: the camera-id table and the
+// residuals of the seen observations.
+// =======================================================================================
+
+// camid[p C + c] = c: the dense slots' camera ids
+__global__ __launch_bounds__(256) void k_bpt_camid(int64_t n_slots, int C, uint8_t* __restrict__ camid) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n_slots) camid[i] = (uint8_t)(i % C);
+}
+
+// residuals of the seen (point, camera) pairs in (point, camera, row) order, behind the board part:
+// that part's length comes from the boards' offsets (k_brd_offsets), where the mask lives
+__global__ __launch_bounds__(256) void k_bpt_resid(int64_t n_slots, int C, int64_t views, int nc,
+                                                   const double* __restrict__ cams, const double* __restrict__ pts,
+                                                   const double2* __restrict__ uv, const uint8_t* __restrict__ mask,
+                                                   const int* __restrict__ poff, const uint8_t* __restrict__ bmask,
+                                                   const int* __restrict__ voff, double* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_slots || !mask[i]) return;
+  const int64_t p = i / C;
+  const int c = (int)(i % C);
+  const size_t base = ((size_t)voff[views - 1] + (bmask[views - 1] ? 1 : 0)) * nc;
+  ProjOut po;
+  fisheye_project<false>(cams + c * ACS_CAM_STRIDE, pts[3 * p], pts[3 * p + 1], pts[3 * p + 2], po);
+  const double2 m = uv[i];
+  double* o = out + (base + poff[i]) * 2;
+  o[0] = po.u - m.x;
+  o[1] = po.v - m.y;
+}
+
+// The device buffers of the mixed solve, one allocation: the boards' (BrdBuffers, with part, Fp and
+// normp long enough for both sides) and the points' behind them.
+struct BptBuffers {
+  BrdBuffers b;
+  double *pts, *Q, *Vg;  // [2][n][3], the slot records, the point blocks
+  uint8_t* cid;
+  int* poff;
+  int nchunk_p;
+};
+
+static size_t bpt_layout(BptBuffers& m, double* base, const BrdDims& d, const ExtDims& dp) {
+  const size_t B = d.B, NC = 6 * d.C, views = B * d.C, n = dp.n, slots = n * d.C;
+  BrdBuffers& b = m.b;
+  Arena a{base};
+  b.nchunk = brd_nchunk(d);
+  m.nchunk_p = n ? ext_nchunk(dp) : 0;
+  b.cams = a.take(2 * (size_t)d.C * ACS_CAM_STRIDE);
+  b.poses = a.take(2 * B * 12);
+  b.Qv = a.take(views * BRD_Q);
+  b.Vb = a.take(B * BRD_V);
+  b.Mb = a.take(B * BRD_M);
+  b.gslot = a.take(B);
+  b.Fp = a.take(B + n);
+  b.part = a.take((b.nchunk + m.nchunk_p) * (NC * NC + 3 * NC));
+  b.dc = a.take(96);
+  b.Sg = a.take(96 * 96);
+  b.db = a.take(6 * B);
+  b.normp = a.take(2 * (B + n));
+  b.camnorm = a.take(64);
+  b.st = a.take<ExtState>(16);
+  b.bad = a.take<int>(2);
+  b.voff = a.take<int>((views + 1) / 2);
+  m.pts = a.take(6 * n);
+  m.Q = a.take(slots * EXT_Q<true>);
+  m.Vg = a.take(n * 10);
+  m.cid = a.take<uint8_t>((slots + 7) / 8);
+  m.poff = a.take<int>((slots + 1) / 2);
+  return a.bytes();
+}
+
+// the point slots as the kernels of sba_ext.hip take them
+struct BptSlots {
+  const double2* uv;
+  const uint8_t* mask;
+};
+
+// one LM iteration of the mixed solve; dp: the points' dimensions (n = 0: the board kernels alone),
+// de carries (B + n, C) to k_ext_solve / k_ext_cam / k_ext_lm
+static void bpt_enqueue(hipStream_t s, const BrdDims& d, const ExtDims& dp, const ExtDims& de, const ExtOpts& o,
+                        const BptBuffers& m, const double* obj, const double2* uv, const uint8_t* mask,
+                        const BptSlots& ps) {
+  const BrdBuffers& b = m.b;
+  const int bgrid = acs_grid(d.B, 256), NC = 6 * d.C, nE = NC * NC + 3 * NC;
+  const bool pts = dp.n > 0;
+  hipLaunchKernelGGL(k_brd_linearize, dim3(d.B), dim3(256), 0, s, d, b.st, b.cams, b.poses, obj, uv, mask, b.Qv, b.Vb);
+  if (pts) ext_launch_linearize(s, dp, b.st, b.cams, m.pts, ps.uv, ps.mask, m.cid, m.Q, m.Vg, b.Fp + d.B);
+  const int nslice = acs_grid(nE, 256);  // one entry per thread
+  hipLaunchKernelGGL(k_brd_schur, dim3(b.nchunk, nslice), dim3(256), brd_schur_lds(d), s, d, b.st, b.Qv, b.Vb, mask,
+                     b.Mb, b.gslot, b.part);
+  if (pts) ext_launch_schur(s, dp, b.st, m.Q, m.Vg, ps.mask, m.cid, b.part + (size_t)b.nchunk * nE);
+  ext_launch_solve(s, de, b.st, b.part, b.nchunk + m.nchunk_p, pts ? m.Vg : nullptr, dp.n, b.gslot, d.B, b.dc, b.Sg,
+                   b.bad);
+  hipLaunchKernelGGL(k_brd_back, dim3(bgrid), dim3(256), 0, s, d, b.st, b.Qv, b.Vb, b.Mb, mask, b.dc, b.poses, b.db,
+                     b.normp);
+  if (pts) ext_launch_back(s, dp, b.st, m.Q, m.Vg, ps.mask, m.cid, b.dc, m.pts, b.normp + 2 * (size_t)d.B);
+  hipLaunchKernelGGL(k_brd_pose, dim3(bgrid), dim3(256), 0, s, d, b.st, b.db, b.poses);
+  ext_launch_cam(s, de, b.st, b.dc, b.cams, b.camnorm);
+  brd_launch_cost(s, d, b, obj, uv, mask, 1);
+  if (pts) ext_launch_point_cost(s, dp, b.st, 1, b.cams, m.pts, ps.uv, ps.mask, m.cid, b.Fp + d.B);
+  ext_launch_lm(s, de, b.st, o, 0, b.Fp, b.normp, b.camnorm);
+}
+
+extern "C" {
+
+int acs_sba_boards_points(acs_ctx* ctx, double* cams, int32_t n_cams, const double* obj_pts, int32_t n_corners,
+                          const double* uv, const uint8_t* mask, int32_t n_boards, double* board_poses,
+                          const double* pt_uv, const uint8_t* pt_mask, int32_t n_pts, double* pts,
+                          const acs_sba_ext_opts* opts, double* resid_before, double* resid_after,
+                          acs_sba_ext_report* report, uint32_t flags) {
+  ACS_DEVICE_GUARD(ctx);
+  ACS_FISHEYE_ONLY(ctx, flags, "acs_sba_boards_points");
+  acs_sba_ext_opts op;
+  acs_sba_ext_default_opts(&op);
+  if (opts) op = *opts;
+  ACS_CHECK(ctx, n_cams >= 1 && n_cams <= EXT_MAXC, "acs_sba_boards_points: n_cams=%d (1..%d)", n_cams, EXT_MAXC);
+  ACS_CHECK(ctx, n_corners >= 3 && n_corners <= BRD_MAXNC, "acs_sba_boards_points: n_corners=%d (3..%d)", n_corners,
+            BRD_MAXNC);
+  ACS_CHECK(ctx, n_boards >= 1, "acs_sba_boards_points: n_boards=%d (>= 1)", n_boards);
+  ACS_CHECK(ctx, n_pts >= 0 && (int64_t)n_pts * n_cams < (int64_t)INT32_MAX,
+            "acs_sba_boards_points: n_pts=%d (>= 0, n_pts n_cams < 2^31)", n_pts);
+  ACS_CHECK(ctx, op.f_scale > 0, "acs_sba_boards_points: f_scale=%g (> 0)", op.f_scale);
+  ACS_CHECK(ctx, cams && obj_pts && uv && mask && board_poses, "acs_sba_boards_points: null array");
+  ACS_CHECK(ctx, n_pts == 0 || (pt_uv && pt_mask && pts), "acs_sba_boards_points: null point array with n_pts=%d",
+            n_pts);
+  hipStream_t s = ctx->stream;
+  const BrdDims d = brd_dims(n_boards, n_cams, n_corners, op.f_scale);
+  ExtDims dp = ext_dims(n_pts, n_cams, n_cams, op.f_scale);
+  const ExtDims de{n_boards + n_pts, 1, n_cams, 2, 1, d.f2};
+  const size_t views = (size_t)n_boards * n_cams, slots = (size_t)n_pts * n_cams;
+  const size_t cam_bytes = sizeof(double) * ACS_CAM_STRIDE * n_cams, pose_bytes = sizeof(double) * 12 * n_boards;
+  const size_t pts_bytes = sizeof(double) * 3 * n_pts;
+  int rc;
+  void *dcams, *dobj, *duv, *dmask, *dposes, *dpuv = nullptr, *dpmask = nullptr, *dpts = nullptr;
+  if ((rc = acs_stage_in(ctx, WS_CAMS, cams, cam_bytes, flags, &dcams))) return rc;
+  if ((rc = acs_stage_in(ctx, WS_PTS, obj_pts, sizeof(double) * 3 * n_corners, flags, &dobj))) return rc;
+  if ((rc = acs_stage_in(ctx, WS_UV, uv, sizeof(double) * 2 * views * n_corners, flags, &duv))) return rc;
+  if ((rc = acs_stage_in(ctx, WS_MASK, mask, views, flags, &dmask))) return rc;
+  if ((rc = acs_stage_in(ctx, WS_TMP0, board_poses, pose_bytes, flags, &dposes))) return rc;
+  if (n_pts > 0) {  // the dense arrays are the slot tensor: slots of their own, beside the boards'
+    if ((rc = acs_stage_in(ctx, WS_TMP1, pt_uv, sizeof(double) * 2 * slots, flags, &dpuv))) return rc;
+    if ((rc = acs_stage_in(ctx, WS_TMP2, pt_mask, slots, flags, &dpmask))) return rc;
+    if ((rc = acs_stage_in(ctx, WS_TMP3, pts, pts_bytes, flags, &dpts))) return rc;
+  }
+  const double* obj = (const double*)dobj;
+  const double2* uvp = (const double2*)duv;
+  const uint8_t* mk = (const uint8_t*)dmask;
+  const BptSlots ps{(const double2*)dpuv, (const uint8_t*)dpmask};
+  BptBuffers m;
+  double* arena = (double*)acs_ws(ctx, WS_FTE6, bpt_layout(m, nullptr, d, dp));
+  if (!arena) return ACS_E_NOMEM;
+  bpt_layout(m, arena, d, dp);
+  const BrdBuffers& b = m.b;
+  // the residual vectors' length: the seen views and point observations, counted where the masks live
+  size_t n_res = 0;
+  const int64_t n_thr = (int64_t)views * n_corners;
+  if (resid_before || resid_after) {
+    hipLaunchKernelGGL(k_brd_offsets, dim3(1), dim3(256), 0, s, (int)views, mk, b.voff);
+    if (n_pts > 0) hipLaunchKernelGGL(k_brd_offsets, dim3(1), dim3(256), 0, s, (int)slots, ps.mask, m.poff);
+    if (!(flags & ACS_DEVICE_PTRS)) {  // with device pointers the caller's arrays hold them all
+      for (size_t v = 0; v < views; ++v) n_res += mask[v] ? n_corners : 0;
+      for (size_t v = 0; v < slots; ++v) n_res += pt_mask[v] ? 1 : 0;
+    }
+  }
+  const size_t res_bytes = sizeof(double) * 2 * n_res;
+  for (int k = 0; k < 2; ++k) {
+    ACS_HIP(ctx, hipMemcpyAsync(b.cams + k * n_cams * ACS_CAM_STRIDE, dcams, cam_bytes, hipMemcpyDeviceToDevice, s));
+    ACS_HIP(ctx, hipMemcpyAsync(b.poses + (size_t)k * n_boards * 12, dposes, pose_bytes, hipMemcpyDeviceToDevice, s));
+    if (n_pts > 0)
+      ACS_HIP(ctx, hipMemcpyAsync(m.pts + (size_t)k * n_pts * 3, dpts, pts_bytes, hipMemcpyDeviceToDevice, s));
+  }
+  if (n_pts > 0) hipLaunchKernelGGL(k_bpt_camid, dim3(acs_grid(slots, 256)), dim3(256), 0, s, (int64_t)slots, n_cams, m.cid);
+  ACS_HIP(ctx, hipMemsetAsync(b.bad, 0, sizeof(int), s));
+  ExtState hs;
+  std::memset(&hs, 0, sizeof(hs));
+  hs.lam = op.lambda0;
+  hs.relin = 1;
+  ACS_HIP(ctx, hipMemcpyAsync(b.st, &hs, sizeof(hs), hipMemcpyHostToDevice, s));
+  auto resid = [&](const double* c, const double* poses, const double* x, double* out) {
+    hipLaunchKernelGGL(k_brd_resid, dim3(acs_grid(n_thr, 256)), dim3(256), 0, s, d, c, poses, obj, uvp, mk, b.voff, out);
+    if (n_pts > 0)
+      hipLaunchKernelGGL(k_bpt_resid, dim3(acs_grid(slots, 256)), dim3(256), 0, s, (int64_t)slots, n_cams,
+                         (int64_t)views, n_corners, c, x, ps.uv, ps.mask, m.poff, mk, b.voff, out);
+  };
+  double* drb = nullptr;
+  if (resid_before) {
+    drb = (double*)acs_out_buf(ctx, WS_OUT0, resid_before, res_bytes, flags);
+    if (!drb) return ACS_E_NOMEM;
+    resid(b.cams, b.poses, m.pts, drb);
+  }
+  ExtOpts o{op.max_iters, op.ftol, op.xtol, op.gtol};
+  brd_launch_cost(s, d, b, obj, uvp, mk, 0);
+  if (n_pts > 0) ext_launch_point_cost(s, dp, b.st, 0, b.cams, m.pts, ps.uv, ps.mask, m.cid, b.Fp + n_boards);
+  ext_launch_lm(s, de, b.st, o, 1, b.Fp, b.normp, b.camnorm);
+  ACS_HIP(ctx, hipGetLastError());
+  // the iterations in groups of four (a linear chain, captured once), the status read per group
+  const int group = 4;
+  hipGraph_t graph = nullptr;
+  hipGraphExec_t exec = nullptr;
+  bool use_graph = op.max_iters > 0 && hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed) == hipSuccess;
+  if (use_graph) {
+    for (int c = 0; c < group; ++c) bpt_enqueue(s, d, dp, de, o, m, obj, uvp, mk, ps);
+    if (hipStreamEndCapture(s, &graph) != hipSuccess ||
+        hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) {
+      if (graph) (void)hipGraphDestroy(graph);
+      (void)hipGetLastError();
+      graph = nullptr;
+      exec = nullptr;
+      use_graph = false;
+    }
+  }
+  for (int it = 0; it < op.max_iters; it += group) {
+    if (use_graph) {
+      ACS_HIP(ctx, hipGraphLaunch(exec, s));
+    } else {
+      for (int c = 0; c < group; ++c) bpt_enqueue(s, d, dp, de, o, m, obj, uvp, mk, ps);
+    }
+    ACS_HIP(ctx, hipGetLastError());
+    ACS_HIP(ctx, hipMemcpyAsync(&hs, b.st, sizeof(hs), hipMemcpyDeviceToHost, s));
+    ACS_HIP(ctx, hipStreamSynchronize(s));
+    if (hs.status != 0) break;
+  }
+  if (exec) (void)hipGraphExecDestroy(exec);
+  if (graph) (void)hipGraphDestroy(graph);
+  if (op.max_iters <= 0) {
+    ACS_HIP(ctx, hipMemcpyAsync(&hs, b.st, sizeof(hs), hipMemcpyDeviceToHost, s));
+    ACS_HIP(ctx, hipStreamSynchronize(s));
+  }
+  const double* fcams = b.cams + hs.cur * n_cams * ACS_CAM_STRIDE;
+  const double* fposes = b.poses + (size_t)hs.cur * n_boards * 12;
+  const double* fpts = m.pts + (size_t)hs.cur * n_pts * 3;
+  const hipMemcpyKind kout = (flags & ACS_DEVICE_PTRS) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  if (resid_after) {
+    double* dra = (double*)acs_out_buf(ctx, WS_OUT1, resid_after, res_bytes, flags);
+    if (!dra) return ACS_E_NOMEM;
+    resid(fcams, fposes, fpts, dra);
+    ACS_HIP(ctx, hipGetLastError());
+    if ((rc = acs_stage_out(ctx, resid_after, dra, res_bytes, flags))) return rc;
+  }
+  if (resid_before && (rc = acs_stage_out(ctx, resid_before, drb, res_bytes, flags))) return rc;
+  ACS_HIP(ctx, hipMemcpyAsync(cams, fcams, cam_bytes, kout, s));
+  ACS_HIP(ctx, hipMemcpyAsync(board_poses, fposes, pose_bytes, kout, s));
+  if (n_pts > 0) ACS_HIP(ctx, hipMemcpyAsync(pts, fpts, pts_bytes, kout, s));
+  int nbad = 0;
+  ACS_HIP(ctx, hipMemcpyAsync(&nbad, b.bad, sizeof(int), hipMemcpyDeviceToHost, s));
+  ACS_HIP(ctx, hipStreamSynchronize(s));
+  if (report) ext_report(report, hs, nbad);
+  return ACS_OK;
+}
+
+}  // extern "C"

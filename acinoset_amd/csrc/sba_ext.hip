@@ -504,6 +504,39 @@ static void ext_enqueue(hipStream_t s, const ExtDims& d, const ExtOpts& o, const
   ext_launch_lm(s, d, b.st, o, 0, b.Fp, b.normp, b.camnorm);
 }
 
+// the point side of the rigid-board SBA with free points (sba_boards.hip, declared in sba_ext.hpp):
+// the same kernels on the caller's buffers, one launch each
+void ext_launch_linearize(hipStream_t s, const ExtDims& d, const ExtState* st, const double* cams, const double* pts,
+                          const double2* uv, const uint8_t* mask, const uint8_t* camid, double* Q, double* Vg,
+                          double* Fp) {
+  const int blocks = acs_grid((int64_t)d.n * d.G, 256);
+#define EXT_LIN(g) \
+  hipLaunchKernelGGL((k_ext_linearize<g>), dim3(blocks), dim3(256), 0, s, d, st, cams, pts, uv, mask, camid, Q, Vg, Fp)
+  ACS_G_SWITCH(d.G, EXT_LIN)
+#undef EXT_LIN
+}
+
+void ext_launch_schur(hipStream_t s, const ExtDims& d, const ExtState* st, const double* Q, const double* Vg,
+                      const uint8_t* mask, const uint8_t* camid, double* part) {
+  hipLaunchKernelGGL(k_ext_schur, dim3(ext_nchunk(d)), dim3(256), ext_schur_lds(d, 3), s, d, st, Q, Vg, mask, camid,
+                     part);
+}
+
+void ext_launch_back(hipStream_t s, const ExtDims& d, const ExtState* st, const double* Q, const double* Vg,
+                     const uint8_t* mask, const uint8_t* camid, const double* dc, double* pts, double* normp) {
+  hipLaunchKernelGGL(k_ext_back, dim3(acs_grid(d.n, 256)), dim3(256), 0, s, d, st, Q, Vg, mask, camid, dc, pts, normp);
+}
+
+void ext_launch_point_cost(hipStream_t s, const ExtDims& d, const ExtState* st, int which, const double* cams,
+                           const double* pts, const double2* uv, const uint8_t* mask, const uint8_t* camid,
+                           double* Fp) {
+  const int blocks = acs_grid((int64_t)d.n * d.G, 256);
+#define EXT_COST(g) \
+  hipLaunchKernelGGL((k_ext_cost<g>), dim3(blocks), dim3(256), 0, s, d, st, which, cams, pts, uv, mask, camid, Fp)
+  ACS_G_SWITCH(d.G, EXT_COST)
+#undef EXT_COST
+}
+
 void ext_report(acs_sba_ext_report* report, const ExtState& hs, int nbad) {
   report->status = hs.status == 0 ? ACS_STATUS_MAXITER : hs.status;
   report->iters = hs.iters;

@@ -74,6 +74,22 @@ void ext_launch_lm(hipStream_t s, const ExtDims& d, ExtState* st, const ExtOpts&
                    const double* normp, const double* camnorm);
 void ext_report(acs_sba_ext_report* report, const ExtState& hs, int nbad);
 
+// The point side, for the rigid-board SBA with free points (acs_sba_boards_points): k_ext_linearize,
+// k_ext_schur (ext_nchunk(d) partials from part), k_ext_back and k_ext_cost as they are, on the
+// caller's buffers. cams [2][C] records and pts [2][n][3] are the current and the trial state that
+// st->cur selects; uv / mask / camid the slot tensor (n, K); Q (n K EXT_Q<true>), Vg (n, 10),
+// Fp (n), normp (2 n).
+void ext_launch_linearize(hipStream_t s, const ExtDims& d, const ExtState* st, const double* cams, const double* pts,
+                          const double2* uv, const uint8_t* mask, const uint8_t* camid, double* Q, double* Vg,
+                          double* Fp);
+void ext_launch_schur(hipStream_t s, const ExtDims& d, const ExtState* st, const double* Q, const double* Vg,
+                      const uint8_t* mask, const uint8_t* camid, double* part);
+void ext_launch_back(hipStream_t s, const ExtDims& d, const ExtState* st, const double* Q, const double* Vg,
+                     const uint8_t* mask, const uint8_t* camid, const double* dc, double* pts, double* normp);
+void ext_launch_point_cost(hipStream_t s, const ExtDims& d, const ExtState* st, int which, const double* cams,
+                           const double* pts, const double2* uv, const uint8_t* mask, const uint8_t* camid,
+                           double* Fp);
+
 // double E[9] = exp([w]x), row-major (Rodrigues; the identity below |w| = 1e-300), declared in the
 // caller's scope. The text of k_ext_cam's update, shared with k_brd_pose (sba_boards.hip); a macro,
 // not a function: as an inlined function the same statements give k_ext_cam other registers.

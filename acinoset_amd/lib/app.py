@@ -35,14 +35,19 @@ def sba_board_points_fisheye(scene_fpath, points_fpaths, out_fpath, manual_point
 
 
 def sba_board_poses_fisheye(scene_fpath, points_fpaths, out_fpath, camera_indices=None, covariance=False,
-                            sigma_px=1.0):
+                            sigma_px=1.0, manual_points_fpath=None):
     """Extrinsics refined with one rigid pose per board image and the known square length
     (`_sba_board_poses`): the scene JSON at out_fpath and `<out_fpath stem>_boards.json` beside it.
-    Hand-labelled manual points are not part of this solve. `covariance=True` also writes
-    `<out_fpath stem>_cov.json` and the board pose covariances into `_boards.json`; the scene JSON
-    is the same file either way."""
+    `covariance=True` also writes `<out_fpath stem>_cov.json` and the board pose covariances into
+    `_boards.json`; the scene JSON is the same file either way.
+    `manual_points_fpath`: hand-labelled points (manual_points.json) solved as free 3-D points in the
+    same solve (acs_sba_boards_points); they tie together cameras that never see the same board
+    image. `_boards.json` then lists them under `manual_points`. Not together with `covariance`
+    (ValueError: the covariance describes the boards-only problem), and there is no
+    manual-points-only form: points alone carry no scale (`sba_board_points_fisheye` covers it).
+    Without a file every output is byte-equal to the call without the argument."""
     return _sba_board_poses(scene_fpath, points_fpaths, out_fpath, camera_indices, covariance=covariance,
-                            sigma_px=sigma_px)
+                            sigma_px=sigma_px, manual_points_fpath=manual_points_fpath)
 
 
 def _gaze_targets(head_pos, nose_pos, r_eye_pos, r=3.0):

@@ -475,8 +475,35 @@ def prepare_calib_boards_for_bundle_adjustment(img_pts_arr, fnames_arr, board_sh
     return uv, mask, obj, board_r, board_t, names
 
 
+def prepare_manual_points_dense(manual_points, k_arr, d_arr, r_arr, t_arr):
+    """The dense form of prepare_manual_points_for_bundle_adjustment for the rigid-board SBA with free
+    points, with its rule: manual_points (n_points, n_cams, 2) with NaN where a camera did not label
+    the point; a point seen by >= 2 cameras is kept and initialised from its first two cameras, all of
+    them in one GPU triangulation batch. Returns (pt_uv (n, C, 2) float64, zero where unseen; pt_mask
+    (n, C) uint8; points_3d (n, 3) float64; kept, the indices of the kept points in the file). The
+    points are a separate input of the solve, so the reference's index offset (`manual +
+    board.max()`) has no counterpart here."""
+    pts = np.asarray(manual_points, np.float64)
+    if pts.ndim != 3 or pts.shape[2] != 2:
+        raise ValueError(f'manual points must be (n_points, n_cams, 2), got {pts.shape}')
+    if pts.shape[1] != len(k_arr):
+        raise ValueError(f'manual points are labelled in {pts.shape[1]} cameras, the scene has {len(k_arr)}')
+    seen = ~np.isnan(pts).any(axis=2)
+    kept = np.nonzero(seen.sum(1) >= 2)[0]
+    pt_mask = np.ascontiguousarray(seen[kept], np.uint8)
+    pt_uv = np.where(pt_mask[:, :, None] != 0, pts[kept], 0.0)
+    jobs = []
+    for i in range(len(kept)):
+        a, b = np.nonzero(pt_mask[i])[0][:2]
+        jobs.append((pt_uv[i, a], pt_uv[i, b], int(a), int(b)))
+    tri = _triangulate_batch(jobs, k_arr, d_arr, r_arr, t_arr, None)
+    points_3d = np.concatenate(tri).astype(np.float64) if tri else np.zeros((0, 3))
+    return pt_uv, pt_mask, points_3d, kept
+
+
 def bundle_adjust_boards_and_extrinsics(uv, mask, obj_pts, board_r, board_t, k_arr, d_arr, r_arr, t_arr, f_scale=1.0,
-                                        covariance=False, sigma_px=1.0, gauge='anchor', anchor=None, **opts):
+                                        covariance=False, sigma_px=1.0, gauge='anchor', anchor=None, points_uv=None,
+                                        points_mask=None, points_3d=None, **opts):
     """acs_sba_boards: every camera's rotation and translation (intrinsics fixed, fisheye model) and one
     rigid pose per board image refined together on the Cauchy objective of
     bundle_adjust_points_and_extrinsics. The known board geometry fixes the metric scale. uv
@@ -491,20 +518,44 @@ def bundle_adjust_boards_and_extrinsics(uv, mask, obj_pts, board_r, board_t, k_a
     a board that is not OK); `cov_status` (B,) and `cov_report` (with 'gauge' and 'anchor'). gauge
     'anchor' holds the pose of camera `anchor` (default 0) and nothing else: the board fixes the
     scale; 'free' is the inner-constraint gauge. The poses and residuals are those of the plain
-    call."""
+    call.
+    With free points (points_uv (n, C, 2), points_mask (n, C), points_3d (n, 3): the arrays of
+    prepare_manual_points_dense) they are solved in the same LM (acs_sba_boards_points). The 5-tuple
+    keeps its shape; the dict gains `points_3d` (n, 3), the refined points, and `n_board_residuals`:
+    `before` / `after` hold the board residuals up to it, then the seen (point, camera) pairs in
+    (point, camera, row) order. Together with `covariance` this raises ValueError before any solve:
+    acs_sba_boards_covariance describes the boards-only problem, and its answer would be silently too
+    wide."""
+    with_points = points_uv is not None or points_mask is not None or points_3d is not None
+    if with_points and (points_uv is None or points_mask is None or points_3d is None):
+        raise ValueError('points_uv, points_mask and points_3d go together')
+    if with_points and covariance:
+        raise ValueError('covariance=True describes the boards-only problem (acs_sba_boards_covariance): '
+                         'not available together with free points')
     ctx = _native.default_context()
     n = len(k_arr)
     o = ctx.sba_ext_opts(f_scale=float(f_scale), **opts)
     t0 = time()
-    cams, br, bt, rb, ra, rep = ctx.sba_boards(_cams(k_arr, d_arr, r_arr, t_arr), obj_pts, uv, mask, board_r, board_t, o)
+    if with_points:
+        if np.shape(points_mask) != (len(np.asarray(points_3d).reshape(-1, 3)), n):
+            raise ValueError(f'points_mask {np.shape(points_mask)} does not match {n} cameras and the points')
+        cams, br, bt, px, rb, ra, rep = ctx.sba_boards_points(_cams(k_arr, d_arr, r_arr, t_arr), obj_pts, uv, mask,
+                                                              board_r, board_t, points_uv, points_mask, points_3d, o)
+    else:
+        cams, br, bt, rb, ra, rep = ctx.sba_boards(_cams(k_arr, d_arr, r_arr, t_arr), obj_pts, uv, mask, board_r,
+                                                   board_t, o)
     t1 = time()
+    extra = f', {len(px)} free points with {int(np.count_nonzero(points_mask))} observations' if with_points else ''
     print(f'GPU SBA (boards + extrinsics): {len(br)} boards of {len(np.asarray(obj_pts).reshape(-1, 3))} corners, '
-          f'{int(np.count_nonzero(mask))} views, {n} cameras, {rep["iters"]} iterations, cost '
+          f'{int(np.count_nonzero(mask))} views{extra}, {n} cameras, {rep["iters"]} iterations, cost '
           f'{rep["cost_before"]:.6e} -> {rep["cost_after"]:.6e} ({rep["status_name"]})')
     print(f'\nOptimization took {t1 - t0:.2f} seconds')
     r_out = cams[:, 8:17].reshape(n, 3, 3).copy()
     t_out = cams[:, 17:20].reshape(n, 3, 1).copy()
     res = dict(before=rb, after=ra, report=rep)
+    if with_points:
+        res.update(points_3d=px, n_board_residuals=2 * len(np.asarray(obj_pts).reshape(-1, 3))
+                   * int(np.count_nonzero(mask)))
     if covariance:
         a = 0 if anchor is None else int(anchor)
         cc, cb, cst, crep = ctx.sba_boards_covariance(cams, obj_pts, uv, mask, br, bt, f_scale=float(f_scale),
@@ -518,14 +569,23 @@ def bundle_adjust_boards_and_extrinsics(uv, mask, obj_pts, board_r, board_t, k_a
     return br, bt, r_out, t_out, res
 
 
-def _sba_board_poses(scene_fpath, points_fpaths, out_fpath, camera_indices=None, covariance=False, sigma_px=1.0):
+def _sba_board_poses(scene_fpath, points_fpaths, out_fpath, camera_indices=None, covariance=False, sigma_px=1.0,
+                     manual_points_fpath=None):
     """Board corners -> rigid-board SBA (bundle_adjust_boards_and_extrinsics) -> refined scene JSON at
     out_fpath and `<out_fpath stem>_boards.json` beside it: per board image its name, pose (r, t) and
     view count, and the report. The square length is the points files'. Returns the residual dict.
     `covariance=True` also writes `<out_fpath stem>_cov.json` (save_pose_covariance: camera 0 held,
     nothing else; camera blocks, sds, centres and centre covariances) and gives each board entry of
     `_boards.json` its `cov` (6 x 6, (dw_b, dt_b)), `rotation_sd`, `translation_sd` and `status`
-    (NaN written as null). The scene file is the same either way."""
+    (NaN written as null). The scene file is the same either way.
+    `manual_points_fpath`: the hand-labelled points of that file (prepare_manual_points_dense) are free
+    points of the same solve; `_boards.json` gains `manual_points`: per kept point its index in the
+    file, refined `xyz` and `n_views`, and `report` covers the mixed solve. ValueError, before anything
+    is solved or written, together with `covariance` or when the file's camera count is not the
+    scene's. Without a file every output file is byte-equal to the call without the argument."""
+    if manual_points_fpath is not None and covariance:
+        raise ValueError('covariance=True describes the boards-only problem: not available together with '
+                         'manual_points_fpath')
     img_pts_arr, fnames_arr, board_shape, square_len = [], [], None, None
     if camera_indices is None:
         camera_indices = range(len(points_fpaths))
@@ -539,6 +599,11 @@ def _sba_board_poses(scene_fpath, points_fpaths, out_fpath, camera_indices=None,
     uv, mask, obj, br, bt, names = prepare_calib_boards_for_bundle_adjustment(img_pts_arr, fnames_arr, board_shape,
                                                                               square_len, k_arr, d_arr, r_arr, t_arr)
     kw = dict(covariance=True, sigma_px=sigma_px) if covariance else {}
+    kept = None
+    if manual_points_fpath is not None:
+        manual_points, _, *_ = load_manual_points(manual_points_fpath)
+        pt_uv, pt_mask, pts_3d, kept = prepare_manual_points_dense(manual_points, k_arr, d_arr, r_arr, t_arr)
+        kw.update(points_uv=pt_uv, points_mask=pt_mask, points_3d=pts_3d)
     br, bt, r_arr, t_arr, res = bundle_adjust_boards_and_extrinsics(uv, mask, obj, br, bt, k_arr, d_arr, r_arr, t_arr,
                                                                     **kw)
     print(f"\nBefore: mean: {np.mean(res['before'])}, std: {np.std(res['before'])}")
@@ -549,6 +614,10 @@ def _sba_board_poses(scene_fpath, points_fpaths, out_fpath, camera_indices=None,
                 parameters='per board X = r p + t: board coordinates to world coordinates (m)',
                 boards=[dict(name=fn, r=br[b].tolist(), t=bt[b].tolist(), n_views=int(mask[b].sum()))
                         for b, fn in enumerate(names)], report=rep)
+    if kept is not None:
+        data['manual_points'] = [dict(index=int(i), xyz=res['points_3d'][k].tolist(), n_views=int(pt_mask[k].sum()))
+                                 for k, i in enumerate(kept)]
+        res.update(points_uv=pt_uv, points_mask=pt_mask, points_kept=kept)
     if covariance:
         save_pose_covariance(os.path.splitext(out_fpath)[0] + '_cov.json', res, r_arr, t_arr, sigma_px)
         names_st = ('ok', 'noobs', 'degenerate')

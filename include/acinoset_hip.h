@@ -433,6 +433,43 @@ int acs_sba_boards(acs_ctx* ctx, double* cams, int32_t n_cams, const double* obj
                    double* resid_after, acs_sba_ext_report* report, uint32_t flags);
 int32_t acs_sba_boards_chunk(int32_t n_cams);
 
+/* ---- rigid boards with free (hand-labelled) points in the same solve --------------------
+ * Everything of acs_sba_boards stays as it is: fisheye cameras c < C <= 16 with fixed intrinsics,
+ * boards b < B with pose (R_b, t_b), object points p_j, uv (B, C, nc, 2), mask (B, C). Added:
+ *   free points X_p, p = 0..n_pts-1, stored densely like the boards and the manual-points file:
+ *     pt_uv (n_pts, n_cams, 2) pixels, pt_mask (n_pts, n_cams) uint8; a camera sees a point at
+ *     most once (in acs_sba_extrinsics' terms slot = camera, K = C). pts (n_pts, 3) is in/out.
+ *   the same robust cost and weights for every residual (Cauchy with f_scale; Triggs
+ *     wh = max((1 - z) w^2, 0.1 w)): F = F_boards + F_points; U and g_c of a camera sum over its
+ *     board views and its point observations
+ *   one LM, those of acs_sba_boards and acs_sba_extrinsics joined: Marquardt damping on every
+ *     diagonal, M_b as in acs_sba_boards, M_p = (V_p + lam diag V_p + 1e-300 I)^-1 as in
+ *     acs_sba_extrinsics,
+ *       S = sum U + lam D - sum_b W M_b W^T - sum_p W M_p W^T,
+ *       b = -g_c + sum_b W M_b g_b + sum_p W M_p g_p,
+ *     db and dX by back-substitution, gmax = max(|g_c|, |g_b|, |g_p|),
+ *     |d|^2 = sum dc^2 + sum db^2 + sum dX^2, |x|^2 = sum |t_c|^2 + sum |t_b|^2 + sum |X_p|^2;
+ *     accept / reject, the lambda schedule and its floor 1e-7, stops, options, status codes and
+ *     report unchanged
+ *   a point without an observation takes no step and contributes nothing; a board without a view
+ *     behaves as in acs_sba_boards. The 6-DoF rigid gauge stays free (resolved by the damping floor).
+ * resid_before / resid_after (either may be NULL): the board part exactly as acs_sba_boards writes
+ * it, then the seen (point, camera) pairs in (point, camera, row) order, 2 doubles each. Host
+ * pointers, or ACS_DEVICE_PTRS for every array. n_pts = 0 is allowed (the point arrays may be NULL)
+ * and runs the board kernels alone: the bits of acs_sba_boards. A second call of the same size
+ * allocates nothing.
+ * ACS_E_INVALID before anything is staged or allocated: the refusals of acs_sba_boards, n_pts < 0
+ * (or n_pts n_cams >= 2^31), a null point array with n_pts > 0, ACS_CAMS_STANDARD.
+ * Not here: covariances of the mixed problem (acs_sba_boards_covariance describes the boards-only
+ * problem), separate noise scales for clicks and corners, the standard camera model, a
+ * distributed form. */
+int acs_sba_boards_points(acs_ctx* ctx, double* cams, int32_t n_cams, const double* obj_pts,
+                          int32_t n_corners, const double* uv, const uint8_t* mask, int32_t n_boards,
+                          double* board_poses, const double* pt_uv, const uint8_t* pt_mask,
+                          int32_t n_pts, double* pts, const acs_sba_ext_opts* opts,
+                          double* resid_before, double* resid_after, acs_sba_ext_report* report,
+                          uint32_t flags);
+
 /* ---- camera-pose and joint point covariances of the points + extrinsics SBA -----------
  * Evaluated at the cameras (fisheye records, n_cams <= 16) and points passed in; nothing is
  * solved. Observation list as acs_sba_extrinsics.
