@@ -1,5 +1,9 @@
 // sba_boards.hip — bundle adjustment of camera extrinsics AND rigid calibration-board poses
-// on gfx950 (acs_sba_boards).
+// on gfx950 (acs_sba_boards), with free hand-labelled points in the same solve
+// (acs_sba_boards_points, further down). Both entry points are one function, brd_solve: the
+// boards-only solve is the mixed one without points. What the linearisation and the Schur partials
+// share with the covariance (sba_boards_cov.hip) is in sba_boards.hpp; the LM driver loop is
+// ext_lm_loop (sba_ext.hip).
 //
 // The problem (the one definition; also in include/acinoset_hip.h and tests/sba_boards_ref.py):
 //   cameras c = 0..C-1: fisheye records, intrinsics fixed, 1 <= C <= EXT_MAXC
@@ -25,13 +29,15 @@
 // is left free and resolved by the damping floor.
 //
 //   k_brd_linearize [1 block of 4 waves per board] waves strided over the cameras, lanes over the
-//                   corners; ext_obs_blocks per corner; every sum is a group_sum over the wave
-//                   (rounds of 64 corners in order) kept by the lane that owns the entry; the view
-//                   record U (21), W (36), g_c (6) and, summed over the views in camera order, the
-//                   board record V (21), g_b (6), F. No floating-point atomics.
-//   k_brd_schur     [board chunks x entry slices] M_b, the W M tiles (36 doubles per view) in LDS, fixed-order
-//                   chunk partials [S | b | diag U | g_c] in k_ext_solve's layout; per board
-//                   max |g_b| for k_ext_solve's slots argument
+//                   corners (brd_stage, brd_view_sums; sba_boards.hpp); ext_obs_blocks per corner;
+//                   every sum is a group_sum over the wave (rounds of 64 corners in order) kept by
+//                   the lane that owns the entry; the view record U (21), W (36), g_c (6) and,
+//                   summed over the views in camera order, the board record V (21), g_b (6), F. No
+//                   floating-point atomics.
+//   k_brd_schur     [board chunks x entry slices] M_b, the W M tiles (36 doubles per view) in LDS
+//                   (brd_schur_stage), fixed-order chunk partials [S | b | diag U | g_c] in
+//                   k_ext_solve's layout (S by brd_schur_entry); per board max |g_b| for
+//                   k_ext_solve's slots argument
 //   k_ext_solve     (sba_ext.hip, unchanged) camera step
 //   k_brd_back      [boards] board steps db and the norm partials
 //   k_brd_pose      [boards] trial board poses on SO(3) (EXT_EXP_SO3, as k_ext_cam)
@@ -40,57 +46,12 @@
 //   k_ext_lm        (sba_ext.hip, unchanged) accept / reject, lambda, stop tests
 #include <algorithm>
 
-#include "sba_ext.hpp"
+#include "sba_boards.hpp"
 
-// the view record, per (board, camera) slot, and the board record
-enum : int { BRD_Q_U = 0, BRD_Q_W = 21, BRD_Q_GC = 57, BRD_Q = 63 };
+// the board record; the view record is BRD_Q<true> (sba_boards.hpp)
 enum : int { BRD_V_V = 0, BRD_V_G = 21, BRD_V_F = 27, BRD_V = 28 };
 // M_b (36, row-major) and whether the board steps (1.0 / 0.0)
 enum : int { BRD_M_OK = 36, BRD_M = 37 };
-
-struct BrdDims {
-  int B, C, nc, chunk;
-  double f2;
-};
-
-// chunk: boards per Schur block. Per board the W M tiles (36 doubles per camera), M_b and its flag
-// (BRD_M), g_b (6) and a seen flag per camera must fit ~96 KB of LDS (as ext_dims)
-static inline int brd_chunk(int n_cams) {
-  return std::max(1, std::min(EXT_CHUNK, (int)(96 * 1024 / (292 * n_cams + 344))));
-}
-static inline BrdDims brd_dims(int n_boards, int n_cams, int n_corners, double f_scale) {
-  return BrdDims{n_boards, n_cams, n_corners, brd_chunk(n_cams), f_scale * f_scale};
-}
-static inline int brd_nchunk(const BrdDims& d) { return (d.B + d.chunk - 1) / d.chunk; }
-// LDS of a Schur block: per board W M (36 doubles per camera), M_b and its flag, g_b, a seen flag per camera
-static inline size_t brd_schur_lds(const BrdDims& d) {
-  return sizeof(double) * (size_t)d.chunk * (d.C * 36 + BRD_M + 6) + sizeof(int) * (size_t)d.chunk * d.C;
-}
-
-// board pose record: R row-major (9), t (3)
-__device__ __forceinline__ void brd_world(const double* pose, const double* p, double rp[3], double X[3]) {
-  for (int i = 0; i < 3; ++i) {
-    rp[i] = pose[3 * i] * p[0] + pose[3 * i + 1] * p[1] + pose[3 * i + 2] * p[2];
-    X[i] = rp[i] + pose[9 + i];
-  }
-}
-
-// cameras, the board's pose, R_b p_j and X_bj into LDS; ends with a barrier
-__device__ __forceinline__ void brd_stage(const BrdDims& d, const double* __restrict__ cams,
-                                          const double* __restrict__ pose, const double* __restrict__ obj,
-                                          double* s_cam, double* s_rp, double* s_X) {
-  for (int i = threadIdx.x; i < d.C * ACS_CAM_STRIDE; i += blockDim.x) s_cam[i] = cams[i];
-  for (int j = threadIdx.x; j < d.nc; j += blockDim.x) {
-    const double p[3] = {obj[3 * j], obj[3 * j + 1], obj[3 * j + 2]};
-    double rp[3], X[3];
-    brd_world(pose, p, rp, X);
-    for (int i = 0; i < 3; ++i) {
-      s_rp[3 * j + i] = rp[i];
-      s_X[3 * j + i] = X[i];
-    }
-  }
-  __syncthreads();
-}
 
 __global__ __launch_bounds__(256) void k_brd_linearize(BrdDims d, const ExtState* __restrict__ st,
                                                        const double* __restrict__ camsbuf,
@@ -108,64 +69,30 @@ __global__ __launch_bounds__(256) void k_brd_linearize(BrdDims d, const ExtState
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = blockDim.x >> 6;
   for (int c = wave; c < d.C; c += nwave) {
     const size_t view = (size_t)b * d.C + c;
-    double* q = Qv + view * BRD_Q;
+    double* q = Qv + view * BRD_Q<true>;
     if (!mask[view]) {
-      if (lane < BRD_Q) q[lane] = 0.0;
+      if (lane < BRD_Q<true>) q[lane] = 0.0;
       if (lane < BRD_V) s_part[c][lane] = 0.0;
       continue;
     }
-    // entry e of the 91 sums lives in lane e % 64: acc0 for e < 64, acc1 behind it
-    double acc0 = 0.0, acc1 = 0.0;
-    for (int j0 = 0; j0 < d.nc; j0 += 64) {
-      const bool live = j0 + lane < d.nc;
-      const int j = live ? j0 + lane : d.nc - 1;
-      int e = 0;
-      auto add = [&](double v) {
-        const double t = group_sum<64>(live ? v : 0.0);
-        if ((e & 63) == lane) {
-          if (e < 64)
-            acc0 += t;
-          else
-            acc1 += t;
-        }
-        ++e;
-      };
-      ExtObs ob;
-      double qo[EXT_Q<false>];
-      ext_obs_blocks(s_cam + c * ACS_CAM_STRIDE, s_X[3 * j], s_X[3 * j + 1], s_X[3 * j + 2], uv[view * d.nc + j], d.f2,
-                     ob, qo);
-      const double v0 = s_rp[3 * j], v1 = s_rp[3 * j + 1], v2 = s_rp[3 * j + 2];
-      double jb[2][6];
+    // the 91 sums: g_c (6) between W and V, then g_b (6) and the cost
+    BrdLaneSums sums{lane};
+    brd_view_sums(
+        d, s_cam + c * ACS_CAM_STRIDE, s_rp, s_X, uv + view * d.nc, sums,
+        [](const ExtObs& ob, BrdLaneSums& add) {
+          const double wr0 = ob.w[0] * ob.r[0], wr1 = ob.w[1] * ob.r[1];
 #pragma unroll
-      for (int dd = 0; dd < 2; ++dd) {
-        const double* jp = ob.jp[dd];
-        jb[dd][0] = -(jp[1] * v2 - jp[2] * v1);
-        jb[dd][1] = -(jp[2] * v0 - jp[0] * v2);
-        jb[dd][2] = -(jp[0] * v1 - jp[1] * v0);
-        jb[dd][3] = jp[0];
-        jb[dd][4] = jp[1];
-        jb[dd][5] = jp[2];
-      }
-      const double wr0 = ob.w[0] * ob.r[0], wr1 = ob.w[1] * ob.r[1];
+          for (int i = 0; i < 6; ++i) add(wr0 * ob.jc[0][i] + wr1 * ob.jc[1][i]);
+        },
+        [&](const ExtObs& ob, const double jb[2][6], BrdLaneSums& add) {
+          const double wr0 = ob.w[0] * ob.r[0], wr1 = ob.w[1] * ob.r[1];
 #pragma unroll
-      for (int k = 0; k < 21; ++k) add(qo[EXT_Q_U + k]);
-#pragma unroll
-      for (int i = 0; i < 6; ++i)
-#pragma unroll
-        for (int k = 0; k < 6; ++k) add(ob.wh[0] * ob.jc[0][i] * jb[0][k] + ob.wh[1] * ob.jc[1][i] * jb[1][k]);
-#pragma unroll
-      for (int i = 0; i < 6; ++i) add(wr0 * ob.jc[0][i] + wr1 * ob.jc[1][i]);
-#pragma unroll
-      for (int i = 0; i < 6; ++i)
-#pragma unroll
-        for (int k = i; k < 6; ++k) add(ob.wh[0] * jb[0][i] * jb[0][k] + ob.wh[1] * jb[1][i] * jb[1][k]);
-#pragma unroll
-      for (int i = 0; i < 6; ++i) add(wr0 * jb[0][i] + wr1 * jb[1][i]);
-      add(0.5 * d.f2 * (log1p(ob.z[0]) + log1p(ob.z[1])));
-    }
-    if (lane < BRD_Q) q[lane] = acc0;
-    if (lane == 63) s_part[c][0] = acc0;
-    if (lane < BRD_V - 1) s_part[c][1 + lane] = acc1;
+          for (int i = 0; i < 6; ++i) add(wr0 * jb[0][i] + wr1 * jb[1][i]);
+          add(0.5 * d.f2 * (log1p(ob.z[0]) + log1p(ob.z[1])));
+        });
+    if (lane < BRD_Q<true>) q[lane] = sums.acc0;
+    if (lane == 63) s_part[c][0] = sums.acc0;
+    if (lane < BRD_V - 1) s_part[c][1 + lane] = sums.acc1;
   }
   __syncthreads();
   if (threadIdx.x < BRD_V) {
@@ -267,36 +194,18 @@ __global__ __launch_bounds__(256) void k_brd_schur(BrdDims d, const ExtState* __
   }
   for (int i = threadIdx.x; i < nb * d.C; i += blockDim.x) sseen[i] = mask[(size_t)b0 * d.C + i];
   __syncthreads();
-  for (int i = threadIdx.x; i < nb * d.C * 36; i += blockDim.x) {
-    const int t = i / (d.C * 36), r = i % (d.C * 36), c = r / 36, k1 = (r % 36) / 6, k2 = r % 6;
-    double z = 0.0;
-    if (sseen[t * d.C + c] && sM[t * BRD_M + BRD_M_OK] != 0.0) {
-      const double* W = Qv + ((size_t)(b0 + t) * d.C + c) * BRD_Q + BRD_Q_W + k1 * 6;
-      const double* M = sM + t * BRD_M;
-      for (int k = 0; k < 6; ++k) z += W[k] * M[k * 6 + k2];
-    }
-    sZ[i] = z;
-  }
-  __syncthreads();
+  brd_schur_stage<true>(d, b0, nb, Qv, sseen, sZ, [&](int t) -> const double* {
+    return sM[t * BRD_M + BRD_M_OK] != 0.0 ? sM + t * BRD_M : nullptr;
+  });
   for (int e = blockIdx.y * blockDim.x + threadIdx.x; e < nE; e += gridDim.y * blockDim.x) {
     double acc = 0.0;
     if (e < NC * NC) {
-      const int a = e / NC, bb = e % NC, c1 = a / 6, k1 = a % 6, c2 = bb / 6, k2 = bb % 6;
-      for (int t = 0; t < nb; ++t) {
-        if (!sseen[t * d.C + c1] || !sseen[t * d.C + c2]) continue;
-        const double* q1 = Qv + ((size_t)(b0 + t) * d.C + c1) * BRD_Q;
-        if (c1 == c2) acc += q1[BRD_Q_U + upk(k1, k2)];
-        const double* z = sZ + ((size_t)t * d.C + c1) * 36 + k1 * 6;
-        const double* w = Qv + ((size_t)(b0 + t) * d.C + c2) * BRD_Q + BRD_Q_W + k2 * 6;
-        double s = 0.0;
-        for (int k = 0; k < 6; ++k) s += z[k] * w[k];
-        acc -= s;
-      }
+      acc = brd_schur_entry<true>(d, b0, nb, Qv, sZ, sseen, e / NC, e % NC);
     } else {
       const int r = e - NC * NC, kind = r / NC, a = r % NC, c1 = a / 6, k1 = a % 6;
       for (int t = 0; t < nb; ++t) {
         if (!sseen[t * d.C + c1]) continue;
-        const double* q = Qv + ((size_t)(b0 + t) * d.C + c1) * BRD_Q;
+        const double* q = Qv + ((size_t)(b0 + t) * d.C + c1) * BRD_Q<true>;
         if (kind == 0) {  // b = -g_c + Z g_b
           const double* z = sZ + ((size_t)t * d.C + c1) * 36 + k1 * 6;
           double s = 0.0;
@@ -328,7 +237,7 @@ __global__ __launch_bounds__(256) void k_brd_back(BrdDims d, const ExtState* __r
   for (int k = 0; k < 6; ++k) acc[k] = Vb[(size_t)b * BRD_V + BRD_V_G + k];
   for (int c = 0; c < d.C; ++c) {
     if (!mask[(size_t)b * d.C + c]) continue;
-    const double* W = Qv + ((size_t)b * d.C + c) * BRD_Q + BRD_Q_W;
+    const double* W = Qv + ((size_t)b * d.C + c) * BRD_Q<true> + BRD_Q_W;
     for (int k = 0; k < 6; ++k)
       for (int i = 0; i < 6; ++i) acc[k] += W[i * 6 + k] * dc[6 * c + i];
   }
@@ -437,189 +346,6 @@ __global__ __launch_bounds__(256) void k_brd_resid(BrdDims d, const double* __re
   o[1] = po.v - m.y;
 }
 
-// ---------------------------------------------------------------------------------------
-// The device buffers of one solve, one allocation.
-struct BrdBuffers {
-  double *cams, *poses;  // the current and the trial state: [2][C] records, [2][B][12]
-  double *Qv, *Vb, *Mb, *gslot, *Fp, *part, *dc, *Sg, *db, *normp, *camnorm;
-  ExtState* st;
-  int *bad, *voff;
-  int nchunk;
-};
-
-// the buffers at base; with a null base only the size in bytes (Arena)
-static size_t brd_layout(BrdBuffers& b, double* base, const BrdDims& d) {
-  const size_t B = d.B, NC = 6 * d.C, views = B * d.C;
-  Arena a{base};
-  b.nchunk = brd_nchunk(d);
-  b.cams = a.take(2 * (size_t)d.C * ACS_CAM_STRIDE);
-  b.poses = a.take(2 * B * 12);
-  b.Qv = a.take(views * BRD_Q);
-  b.Vb = a.take(B * BRD_V);
-  b.Mb = a.take(B * BRD_M);
-  b.gslot = a.take(B);
-  b.Fp = a.take(B);
-  b.part = a.take(b.nchunk * (NC * NC + 3 * NC));
-  b.dc = a.take(96);
-  b.Sg = a.take(96 * 96);
-  b.db = a.take(6 * B);
-  b.normp = a.take(2 * B);
-  b.camnorm = a.take(64);
-  b.st = a.take<ExtState>(16);
-  b.bad = a.take<int>(2);
-  b.voff = a.take<int>((views + 1) / 2);
-  return a.bytes();
-}
-
-static void brd_launch_cost(hipStream_t s, const BrdDims& d, const BrdBuffers& b, const double* obj, const double2* uv,
-                            const uint8_t* mask, int which) {
-  hipLaunchKernelGGL(k_brd_cost, dim3(d.B), dim3(256), 0, s, d, b.st, which, b.cams, b.poses, obj, uv, mask, b.Fp);
-}
-
-// one LM iteration; de carries (B, C) to the kernels of sba_ext.hip
-static void brd_enqueue(hipStream_t s, const BrdDims& d, const ExtDims& de, const ExtOpts& o, const BrdBuffers& b,
-                        const double* obj, const double2* uv, const uint8_t* mask) {
-  const int bgrid = acs_grid(d.B, 256);
-  hipLaunchKernelGGL(k_brd_linearize, dim3(d.B), dim3(256), 0, s, d, b.st, b.cams, b.poses, obj, uv, mask, b.Qv, b.Vb);
-  const int NC = 6 * d.C, nslice = acs_grid(NC * NC + 3 * NC, 256);  // one entry per thread
-  hipLaunchKernelGGL(k_brd_schur, dim3(b.nchunk, nslice), dim3(256), brd_schur_lds(d), s, d, b.st, b.Qv, b.Vb, mask,
-                     b.Mb, b.gslot, b.part);
-  ext_launch_solve(s, de, b.st, b.part, b.nchunk, nullptr, 0, b.gslot, d.B, b.dc, b.Sg, b.bad);
-  hipLaunchKernelGGL(k_brd_back, dim3(bgrid), dim3(256), 0, s, d, b.st, b.Qv, b.Vb, b.Mb, mask, b.dc, b.poses, b.db,
-                     b.normp);
-  hipLaunchKernelGGL(k_brd_pose, dim3(bgrid), dim3(256), 0, s, d, b.st, b.db, b.poses);
-  ext_launch_cam(s, de, b.st, b.dc, b.cams, b.camnorm);
-  brd_launch_cost(s, d, b, obj, uv, mask, 1);
-  ext_launch_lm(s, de, b.st, o, 0, b.Fp, b.normp, b.camnorm);
-}
-
-extern "C" {
-
-int32_t acs_sba_boards_chunk(int32_t n_cams) { return brd_chunk(n_cams); }
-
-int acs_sba_boards(acs_ctx* ctx, double* cams, int32_t n_cams, const double* obj_pts, int32_t n_corners,
-                   const double* uv, const uint8_t* mask, int32_t n_boards, double* board_poses,
-                   const acs_sba_ext_opts* opts, double* resid_before, double* resid_after,
-                   acs_sba_ext_report* report, uint32_t flags) {
-  ACS_DEVICE_GUARD(ctx);
-  ACS_FISHEYE_ONLY(ctx, flags, "acs_sba_boards");
-  acs_sba_ext_opts op;
-  acs_sba_ext_default_opts(&op);
-  if (opts) op = *opts;
-  ACS_CHECK(ctx, n_cams >= 1 && n_cams <= EXT_MAXC, "acs_sba_boards: n_cams=%d (1..%d)", n_cams, EXT_MAXC);
-  ACS_CHECK(ctx, n_corners >= 3 && n_corners <= BRD_MAXNC, "acs_sba_boards: n_corners=%d (3..%d)", n_corners,
-            BRD_MAXNC);
-  ACS_CHECK(ctx, n_boards >= 1, "acs_sba_boards: n_boards=%d (>= 1)", n_boards);
-  ACS_CHECK(ctx, op.f_scale > 0, "acs_sba_boards: f_scale=%g (> 0)", op.f_scale);
-  ACS_CHECK(ctx, cams && obj_pts && uv && mask && board_poses, "acs_sba_boards: null array");
-  hipStream_t s = ctx->stream;
-  const BrdDims d = brd_dims(n_boards, n_cams, n_corners, op.f_scale);
-  const ExtDims de{n_boards, 1, n_cams, 2, 1, d.f2};
-  const size_t views = (size_t)n_boards * n_cams;
-  const size_t cam_bytes = sizeof(double) * ACS_CAM_STRIDE * n_cams, pose_bytes = sizeof(double) * 12 * n_boards;
-  int rc;
-  void *dcams, *dobj, *duv, *dmask, *dposes;
-  if ((rc = acs_stage_in(ctx, WS_CAMS, cams, cam_bytes, flags, &dcams))) return rc;
-  if ((rc = acs_stage_in(ctx, WS_PTS, obj_pts, sizeof(double) * 3 * n_corners, flags, &dobj))) return rc;
-  if ((rc = acs_stage_in(ctx, WS_UV, uv, sizeof(double) * 2 * views * n_corners, flags, &duv))) return rc;
-  if ((rc = acs_stage_in(ctx, WS_MASK, mask, views, flags, &dmask))) return rc;
-  if ((rc = acs_stage_in(ctx, WS_TMP0, board_poses, pose_bytes, flags, &dposes))) return rc;
-  const double* obj = (const double*)dobj;
-  const double2* uvp = (const double2*)duv;
-  const uint8_t* mk = (const uint8_t*)dmask;
-  BrdBuffers b;
-  double* arena = (double*)acs_ws(ctx, WS_FTE6, brd_layout(b, nullptr, d));
-  if (!arena) return ACS_E_NOMEM;
-  brd_layout(b, arena, d);
-  // the residual vectors' length: the seen views, counted where the mask lives
-  int n_seen = 0;
-  const int64_t n_thr = (int64_t)views * n_corners;
-  if (resid_before || resid_after) {
-    hipLaunchKernelGGL(k_brd_offsets, dim3(1), dim3(256), 0, s, (int)views, mk, b.voff);
-    if (flags & ACS_DEVICE_PTRS) {
-      n_seen = (int)views;  // the caller's arrays hold the seen views; no more than all are written
-    } else {
-      for (size_t v = 0; v < views; ++v) n_seen += mask[v] ? 1 : 0;
-    }
-  }
-  const size_t res_bytes = sizeof(double) * 2 * (size_t)n_seen * n_corners;
-  for (int k = 0; k < 2; ++k) {
-    ACS_HIP(ctx, hipMemcpyAsync(b.cams + k * n_cams * ACS_CAM_STRIDE, dcams, cam_bytes, hipMemcpyDeviceToDevice, s));
-    ACS_HIP(ctx, hipMemcpyAsync(b.poses + (size_t)k * n_boards * 12, dposes, pose_bytes, hipMemcpyDeviceToDevice, s));
-  }
-  ACS_HIP(ctx, hipMemsetAsync(b.bad, 0, sizeof(int), s));
-  ExtState hs;
-  std::memset(&hs, 0, sizeof(hs));
-  hs.lam = op.lambda0;
-  hs.relin = 1;
-  ACS_HIP(ctx, hipMemcpyAsync(b.st, &hs, sizeof(hs), hipMemcpyHostToDevice, s));
-  double* drb = nullptr;
-  if (resid_before) {
-    drb = (double*)acs_out_buf(ctx, WS_OUT0, resid_before, res_bytes, flags);
-    if (!drb) return ACS_E_NOMEM;
-    hipLaunchKernelGGL(k_brd_resid, dim3(acs_grid(n_thr, 256)), dim3(256), 0, s, d, b.cams, b.poses, obj, uvp, mk,
-                       b.voff, drb);
-  }
-  ExtOpts o{op.max_iters, op.ftol, op.xtol, op.gtol};
-  brd_launch_cost(s, d, b, obj, uvp, mk, 0);
-  ext_launch_lm(s, de, b.st, o, 1, b.Fp, b.normp, b.camnorm);
-  ACS_HIP(ctx, hipGetLastError());
-  // the iterations in groups of four (a linear chain, captured once), the status read per group
-  const int group = 4;
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t exec = nullptr;
-  bool use_graph = op.max_iters > 0 && hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed) == hipSuccess;
-  if (use_graph) {
-    for (int c = 0; c < group; ++c) brd_enqueue(s, d, de, o, b, obj, uvp, mk);
-    if (hipStreamEndCapture(s, &graph) != hipSuccess ||
-        hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) {
-      if (graph) (void)hipGraphDestroy(graph);
-      (void)hipGetLastError();
-      graph = nullptr;
-      exec = nullptr;
-      use_graph = false;
-    }
-  }
-  for (int it = 0; it < op.max_iters; it += group) {
-    if (use_graph) {
-      ACS_HIP(ctx, hipGraphLaunch(exec, s));
-    } else {
-      for (int c = 0; c < group; ++c) brd_enqueue(s, d, de, o, b, obj, uvp, mk);
-    }
-    ACS_HIP(ctx, hipGetLastError());
-    ACS_HIP(ctx, hipMemcpyAsync(&hs, b.st, sizeof(hs), hipMemcpyDeviceToHost, s));
-    ACS_HIP(ctx, hipStreamSynchronize(s));
-    if (hs.status != 0) break;
-  }
-  if (exec) (void)hipGraphExecDestroy(exec);
-  if (graph) (void)hipGraphDestroy(graph);
-  if (op.max_iters <= 0) {
-    ACS_HIP(ctx, hipMemcpyAsync(&hs, b.st, sizeof(hs), hipMemcpyDeviceToHost, s));
-    ACS_HIP(ctx, hipStreamSynchronize(s));
-  }
-  const double* fcams = b.cams + hs.cur * n_cams * ACS_CAM_STRIDE;
-  const double* fposes = b.poses + (size_t)hs.cur * n_boards * 12;
-  const hipMemcpyKind kout = (flags & ACS_DEVICE_PTRS) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-  if (resid_after) {
-    double* dra = (double*)acs_out_buf(ctx, WS_OUT1, resid_after, res_bytes, flags);
-    if (!dra) return ACS_E_NOMEM;
-    hipLaunchKernelGGL(k_brd_resid, dim3(acs_grid(n_thr, 256)), dim3(256), 0, s, d, fcams, fposes, obj, uvp, mk, b.voff,
-                       dra);
-    ACS_HIP(ctx, hipGetLastError());
-    if ((rc = acs_stage_out(ctx, resid_after, dra, res_bytes, flags))) return rc;
-  }
-  if (resid_before && (rc = acs_stage_out(ctx, resid_before, drb, res_bytes, flags))) return rc;
-  ACS_HIP(ctx, hipMemcpyAsync(cams, fcams, cam_bytes, kout, s));
-  ACS_HIP(ctx, hipMemcpyAsync(board_poses, fposes, pose_bytes, kout, s));
-  int nbad = 0;
-  ACS_HIP(ctx, hipMemcpyAsync(&nbad, b.bad, sizeof(int), hipMemcpyDeviceToHost, s));
-  ACS_HIP(ctx, hipStreamSynchronize(s));
-  if (report) ext_report(report, hs, nbad);
-  return ACS_OK;
-}
-
-}  // extern "C"
-
 // =======================================================================================
 // Rigid boards with free (hand-labelled) points in the same solve (acs_sba_boards_points).
 //
@@ -643,8 +369,9 @@ int acs_sba_boards(acs_ctx* ctx, double* cams, int32_t n_cams, const double* obj
 // sba_ext.hip's kernels on the dense slots (ext_launch_*), with ext_dims(n, C, C, f_scale). The two
 // sides meet in flat buffers: part holds the board chunks, then the point chunks; Fp and normp the
 // boards, then the points (k_ext_lm sums B + n entries); one ExtState, dc, Sg, bad, camnorm and
-// camera double buffer. New device code is what the dense form needs: the camera-id table and the
-// residuals of the seen observations.
+// camera double buffer. Device code of its own is what the dense form needs: the camera-id table and
+// the residuals of the seen observations. Without points (n = 0) the point launches fall away and what
+// is left is acs_sba_boards, bit for bit: the one host path below (brd_solve) serves both.
 // =======================================================================================
 
 // camid[p C + c] = c: the dense slots' camera ids
@@ -673,30 +400,34 @@ __global__ __launch_bounds__(256) void k_bpt_resid(int64_t n_slots, int C, int64
   o[1] = po.v - m.y;
 }
 
-// The device buffers of the mixed solve, one allocation: the boards' (BrdBuffers, with part, Fp and
-// normp long enough for both sides) and the points' behind them.
-struct BptBuffers {
-  BrdBuffers b;
+// ---------------------------------------------------------------------------------------
+// The device buffers of one solve, one allocation: the boards', with part, Fp and normp long enough
+// for both sides, and the points' behind them (empty without points).
+struct BrdBuffers {
+  double *cams, *poses;  // the current and the trial state: [2][C] records, [2][B][12]
+  double *Qv, *Vb, *Mb, *gslot, *Fp, *part, *dc, *Sg, *db, *normp, *camnorm;
+  ExtState* st;
+  int *bad, *voff;
   double *pts, *Q, *Vg;  // [2][n][3], the slot records, the point blocks
   uint8_t* cid;
   int* poff;
-  int nchunk_p;
+  int nchunk, nchunk_p;
 };
 
-static size_t bpt_layout(BptBuffers& m, double* base, const BrdDims& d, const ExtDims& dp) {
+// the buffers at base; with a null base only the size in bytes (Arena)
+static size_t brd_layout(BrdBuffers& b, double* base, const BrdDims& d, const ExtDims& dp) {
   const size_t B = d.B, NC = 6 * d.C, views = B * d.C, n = dp.n, slots = n * d.C;
-  BrdBuffers& b = m.b;
   Arena a{base};
   b.nchunk = brd_nchunk(d);
-  m.nchunk_p = n ? ext_nchunk(dp) : 0;
+  b.nchunk_p = n ? ext_nchunk(dp) : 0;
   b.cams = a.take(2 * (size_t)d.C * ACS_CAM_STRIDE);
   b.poses = a.take(2 * B * 12);
-  b.Qv = a.take(views * BRD_Q);
+  b.Qv = a.take(views * BRD_Q<true>);
   b.Vb = a.take(B * BRD_V);
   b.Mb = a.take(B * BRD_M);
   b.gslot = a.take(B);
   b.Fp = a.take(B + n);
-  b.part = a.take((b.nchunk + m.nchunk_p) * (NC * NC + 3 * NC));
+  b.part = a.take((b.nchunk + b.nchunk_p) * (NC * NC + 3 * NC));
   b.dc = a.take(96);
   b.Sg = a.take(96 * 96);
   b.db = a.take(6 * B);
@@ -705,71 +436,76 @@ static size_t bpt_layout(BptBuffers& m, double* base, const BrdDims& d, const Ex
   b.st = a.take<ExtState>(16);
   b.bad = a.take<int>(2);
   b.voff = a.take<int>((views + 1) / 2);
-  m.pts = a.take(6 * n);
-  m.Q = a.take(slots * EXT_Q<true>);
-  m.Vg = a.take(n * 10);
-  m.cid = a.take<uint8_t>((slots + 7) / 8);
-  m.poff = a.take<int>((slots + 1) / 2);
+  b.pts = a.take(6 * n);
+  b.Q = a.take(slots * EXT_Q<true>);
+  b.Vg = a.take(n * 10);
+  b.cid = a.take<uint8_t>((slots + 7) / 8);
+  b.poff = a.take<int>((slots + 1) / 2);
   return a.bytes();
 }
 
-// the point slots as the kernels of sba_ext.hip take them
-struct BptSlots {
+// the problem's device arrays: the boards', and the point slots as the kernels of sba_ext.hip take them
+struct BrdInputs {
+  const double* obj;
   const double2* uv;
   const uint8_t* mask;
+  const double2* pt_uv;
+  const uint8_t* pt_mask;
 };
 
-// one LM iteration of the mixed solve; dp: the points' dimensions (n = 0: the board kernels alone),
-// de carries (B + n, C) to k_ext_solve / k_ext_cam / k_ext_lm
-static void bpt_enqueue(hipStream_t s, const BrdDims& d, const ExtDims& dp, const ExtDims& de, const ExtOpts& o,
-                        const BptBuffers& m, const double* obj, const double2* uv, const uint8_t* mask,
-                        const BptSlots& ps) {
-  const BrdBuffers& b = m.b;
+// the robust cost per board and per point: which = 0 at the current state, 1 at the trial
+static void brd_launch_cost(hipStream_t s, const BrdDims& d, const ExtDims& dp, const BrdBuffers& b, const BrdInputs& in,
+                            int which) {
+  hipLaunchKernelGGL(k_brd_cost, dim3(d.B), dim3(256), 0, s, d, b.st, which, b.cams, b.poses, in.obj, in.uv, in.mask,
+                     b.Fp);
+  if (dp.n > 0) ext_launch_point_cost(s, dp, b.st, which, b.cams, b.pts, in.pt_uv, in.pt_mask, b.cid, b.Fp + d.B);
+}
+
+// one LM iteration; dp: the points' dimensions (n = 0: the board kernels alone), de carries
+// (B + n, C) to k_ext_solve / k_ext_cam / k_ext_lm
+static void brd_enqueue(hipStream_t s, const BrdDims& d, const ExtDims& dp, const ExtDims& de, const ExtOpts& o,
+                        const BrdBuffers& b, const BrdInputs& in) {
   const int bgrid = acs_grid(d.B, 256), NC = 6 * d.C, nE = NC * NC + 3 * NC;
   const bool pts = dp.n > 0;
-  hipLaunchKernelGGL(k_brd_linearize, dim3(d.B), dim3(256), 0, s, d, b.st, b.cams, b.poses, obj, uv, mask, b.Qv, b.Vb);
-  if (pts) ext_launch_linearize(s, dp, b.st, b.cams, m.pts, ps.uv, ps.mask, m.cid, m.Q, m.Vg, b.Fp + d.B);
+  hipLaunchKernelGGL(k_brd_linearize, dim3(d.B), dim3(256), 0, s, d, b.st, b.cams, b.poses, in.obj, in.uv, in.mask, b.Qv,
+                     b.Vb);
+  if (pts) ext_launch_linearize(s, dp, b.st, b.cams, b.pts, in.pt_uv, in.pt_mask, b.cid, b.Q, b.Vg, b.Fp + d.B);
   const int nslice = acs_grid(nE, 256);  // one entry per thread
-  hipLaunchKernelGGL(k_brd_schur, dim3(b.nchunk, nslice), dim3(256), brd_schur_lds(d), s, d, b.st, b.Qv, b.Vb, mask,
-                     b.Mb, b.gslot, b.part);
-  if (pts) ext_launch_schur(s, dp, b.st, m.Q, m.Vg, ps.mask, m.cid, b.part + (size_t)b.nchunk * nE);
-  ext_launch_solve(s, de, b.st, b.part, b.nchunk + m.nchunk_p, pts ? m.Vg : nullptr, dp.n, b.gslot, d.B, b.dc, b.Sg,
+  hipLaunchKernelGGL(k_brd_schur, dim3(b.nchunk, nslice), dim3(256), brd_schur_lds(d, BRD_M + 6), s, d, b.st, b.Qv, b.Vb,
+                     in.mask, b.Mb, b.gslot, b.part);
+  if (pts) ext_launch_schur(s, dp, b.st, b.Q, b.Vg, in.pt_mask, b.cid, b.part + (size_t)b.nchunk * nE);
+  ext_launch_solve(s, de, b.st, b.part, b.nchunk + b.nchunk_p, pts ? b.Vg : nullptr, dp.n, b.gslot, d.B, b.dc, b.Sg,
                    b.bad);
-  hipLaunchKernelGGL(k_brd_back, dim3(bgrid), dim3(256), 0, s, d, b.st, b.Qv, b.Vb, b.Mb, mask, b.dc, b.poses, b.db,
+  hipLaunchKernelGGL(k_brd_back, dim3(bgrid), dim3(256), 0, s, d, b.st, b.Qv, b.Vb, b.Mb, in.mask, b.dc, b.poses, b.db,
                      b.normp);
-  if (pts) ext_launch_back(s, dp, b.st, m.Q, m.Vg, ps.mask, m.cid, b.dc, m.pts, b.normp + 2 * (size_t)d.B);
+  if (pts) ext_launch_back(s, dp, b.st, b.Q, b.Vg, in.pt_mask, b.cid, b.dc, b.pts, b.normp + 2 * (size_t)d.B);
   hipLaunchKernelGGL(k_brd_pose, dim3(bgrid), dim3(256), 0, s, d, b.st, b.db, b.poses);
   ext_launch_cam(s, de, b.st, b.dc, b.cams, b.camnorm);
-  brd_launch_cost(s, d, b, obj, uv, mask, 1);
-  if (pts) ext_launch_point_cost(s, dp, b.st, 1, b.cams, m.pts, ps.uv, ps.mask, m.cid, b.Fp + d.B);
+  brd_launch_cost(s, d, dp, b, in, 1);
   ext_launch_lm(s, de, b.st, o, 0, b.Fp, b.normp, b.camnorm);
 }
 
-extern "C" {
-
-int acs_sba_boards_points(acs_ctx* ctx, double* cams, int32_t n_cams, const double* obj_pts, int32_t n_corners,
-                          const double* uv, const uint8_t* mask, int32_t n_boards, double* board_poses,
-                          const double* pt_uv, const uint8_t* pt_mask, int32_t n_pts, double* pts,
-                          const acs_sba_ext_opts* opts, double* resid_before, double* resid_after,
-                          acs_sba_ext_report* report, uint32_t flags) {
-  ACS_DEVICE_GUARD(ctx);
-  ACS_FISHEYE_ONLY(ctx, flags, "acs_sba_boards_points");
+// The solve behind acs_sba_boards (null point arrays, n_pts = 0) and acs_sba_boards_points; fn names
+// the entry point in the error texts. Every check comes before anything is staged or allocated.
+static int brd_solve(acs_ctx* ctx, const char* fn, double* cams, int32_t n_cams, const double* obj_pts,
+                     int32_t n_corners, const double* uv, const uint8_t* mask, int32_t n_boards, double* board_poses,
+                     const double* pt_uv, const uint8_t* pt_mask, int32_t n_pts, double* pts,
+                     const acs_sba_ext_opts* opts, double* resid_before, double* resid_after,
+                     acs_sba_ext_report* report, uint32_t flags) {
   acs_sba_ext_opts op;
   acs_sba_ext_default_opts(&op);
   if (opts) op = *opts;
-  ACS_CHECK(ctx, n_cams >= 1 && n_cams <= EXT_MAXC, "acs_sba_boards_points: n_cams=%d (1..%d)", n_cams, EXT_MAXC);
-  ACS_CHECK(ctx, n_corners >= 3 && n_corners <= BRD_MAXNC, "acs_sba_boards_points: n_corners=%d (3..%d)", n_corners,
-            BRD_MAXNC);
-  ACS_CHECK(ctx, n_boards >= 1, "acs_sba_boards_points: n_boards=%d (>= 1)", n_boards);
-  ACS_CHECK(ctx, n_pts >= 0 && (int64_t)n_pts * n_cams < (int64_t)INT32_MAX,
-            "acs_sba_boards_points: n_pts=%d (>= 0, n_pts n_cams < 2^31)", n_pts);
-  ACS_CHECK(ctx, op.f_scale > 0, "acs_sba_boards_points: f_scale=%g (> 0)", op.f_scale);
-  ACS_CHECK(ctx, cams && obj_pts && uv && mask && board_poses, "acs_sba_boards_points: null array");
-  ACS_CHECK(ctx, n_pts == 0 || (pt_uv && pt_mask && pts), "acs_sba_boards_points: null point array with n_pts=%d",
-            n_pts);
+  ACS_CHECK(ctx, n_cams >= 1 && n_cams <= EXT_MAXC, "%s: n_cams=%d (1..%d)", fn, n_cams, EXT_MAXC);
+  ACS_CHECK(ctx, n_corners >= 3 && n_corners <= BRD_MAXNC, "%s: n_corners=%d (3..%d)", fn, n_corners, BRD_MAXNC);
+  ACS_CHECK(ctx, n_boards >= 1, "%s: n_boards=%d (>= 1)", fn, n_boards);
+  ACS_CHECK(ctx, n_pts >= 0 && (int64_t)n_pts * n_cams < (int64_t)INT32_MAX, "%s: n_pts=%d (>= 0, n_pts n_cams < 2^31)",
+            fn, n_pts);
+  ACS_CHECK(ctx, op.f_scale > 0, "%s: f_scale=%g (> 0)", fn, op.f_scale);
+  ACS_CHECK(ctx, cams && obj_pts && uv && mask && board_poses, "%s: null array", fn);
+  ACS_CHECK(ctx, n_pts == 0 || (pt_uv && pt_mask && pts), "%s: null point array with n_pts=%d", fn, n_pts);
   hipStream_t s = ctx->stream;
   const BrdDims d = brd_dims(n_boards, n_cams, n_corners, op.f_scale);
-  ExtDims dp = ext_dims(n_pts, n_cams, n_cams, op.f_scale);
+  const ExtDims dp = ext_dims(n_pts, n_cams, n_cams, op.f_scale);
   const ExtDims de{n_boards + n_pts, 1, n_cams, 2, 1, d.f2};
   const size_t views = (size_t)n_boards * n_cams, slots = (size_t)n_pts * n_cams;
   const size_t cam_bytes = sizeof(double) * ACS_CAM_STRIDE * n_cams, pose_bytes = sizeof(double) * 12 * n_boards;
@@ -786,21 +522,18 @@ int acs_sba_boards_points(acs_ctx* ctx, double* cams, int32_t n_cams, const doub
     if ((rc = acs_stage_in(ctx, WS_TMP2, pt_mask, slots, flags, &dpmask))) return rc;
     if ((rc = acs_stage_in(ctx, WS_TMP3, pts, pts_bytes, flags, &dpts))) return rc;
   }
-  const double* obj = (const double*)dobj;
-  const double2* uvp = (const double2*)duv;
-  const uint8_t* mk = (const uint8_t*)dmask;
-  const BptSlots ps{(const double2*)dpuv, (const uint8_t*)dpmask};
-  BptBuffers m;
-  double* arena = (double*)acs_ws(ctx, WS_FTE6, bpt_layout(m, nullptr, d, dp));
+  const BrdInputs in{(const double*)dobj, (const double2*)duv, (const uint8_t*)dmask, (const double2*)dpuv,
+                     (const uint8_t*)dpmask};
+  BrdBuffers b;
+  double* arena = (double*)acs_ws(ctx, WS_FTE6, brd_layout(b, nullptr, d, dp));
   if (!arena) return ACS_E_NOMEM;
-  bpt_layout(m, arena, d, dp);
-  const BrdBuffers& b = m.b;
+  brd_layout(b, arena, d, dp);
   // the residual vectors' length: the seen views and point observations, counted where the masks live
   size_t n_res = 0;
   const int64_t n_thr = (int64_t)views * n_corners;
   if (resid_before || resid_after) {
-    hipLaunchKernelGGL(k_brd_offsets, dim3(1), dim3(256), 0, s, (int)views, mk, b.voff);
-    if (n_pts > 0) hipLaunchKernelGGL(k_brd_offsets, dim3(1), dim3(256), 0, s, (int)slots, ps.mask, m.poff);
+    hipLaunchKernelGGL(k_brd_offsets, dim3(1), dim3(256), 0, s, (int)views, in.mask, b.voff);
+    if (n_pts > 0) hipLaunchKernelGGL(k_brd_offsets, dim3(1), dim3(256), 0, s, (int)slots, in.pt_mask, b.poff);
     if (!(flags & ACS_DEVICE_PTRS)) {  // with device pointers the caller's arrays hold them all
       for (size_t v = 0; v < views; ++v) n_res += mask[v] ? n_corners : 0;
       for (size_t v = 0; v < slots; ++v) n_res += pt_mask[v] ? 1 : 0;
@@ -811,9 +544,9 @@ int acs_sba_boards_points(acs_ctx* ctx, double* cams, int32_t n_cams, const doub
     ACS_HIP(ctx, hipMemcpyAsync(b.cams + k * n_cams * ACS_CAM_STRIDE, dcams, cam_bytes, hipMemcpyDeviceToDevice, s));
     ACS_HIP(ctx, hipMemcpyAsync(b.poses + (size_t)k * n_boards * 12, dposes, pose_bytes, hipMemcpyDeviceToDevice, s));
     if (n_pts > 0)
-      ACS_HIP(ctx, hipMemcpyAsync(m.pts + (size_t)k * n_pts * 3, dpts, pts_bytes, hipMemcpyDeviceToDevice, s));
+      ACS_HIP(ctx, hipMemcpyAsync(b.pts + (size_t)k * n_pts * 3, dpts, pts_bytes, hipMemcpyDeviceToDevice, s));
   }
-  if (n_pts > 0) hipLaunchKernelGGL(k_bpt_camid, dim3(acs_grid(slots, 256)), dim3(256), 0, s, (int64_t)slots, n_cams, m.cid);
+  if (n_pts > 0) hipLaunchKernelGGL(k_bpt_camid, dim3(acs_grid(slots, 256)), dim3(256), 0, s, (int64_t)slots, n_cams, b.cid);
   ACS_HIP(ctx, hipMemsetAsync(b.bad, 0, sizeof(int), s));
   ExtState hs;
   std::memset(&hs, 0, sizeof(hs));
@@ -821,58 +554,26 @@ int acs_sba_boards_points(acs_ctx* ctx, double* cams, int32_t n_cams, const doub
   hs.relin = 1;
   ACS_HIP(ctx, hipMemcpyAsync(b.st, &hs, sizeof(hs), hipMemcpyHostToDevice, s));
   auto resid = [&](const double* c, const double* poses, const double* x, double* out) {
-    hipLaunchKernelGGL(k_brd_resid, dim3(acs_grid(n_thr, 256)), dim3(256), 0, s, d, c, poses, obj, uvp, mk, b.voff, out);
+    hipLaunchKernelGGL(k_brd_resid, dim3(acs_grid(n_thr, 256)), dim3(256), 0, s, d, c, poses, in.obj, in.uv, in.mask,
+                       b.voff, out);
     if (n_pts > 0)
       hipLaunchKernelGGL(k_bpt_resid, dim3(acs_grid(slots, 256)), dim3(256), 0, s, (int64_t)slots, n_cams,
-                         (int64_t)views, n_corners, c, x, ps.uv, ps.mask, m.poff, mk, b.voff, out);
+                         (int64_t)views, n_corners, c, x, in.pt_uv, in.pt_mask, b.poff, in.mask, b.voff, out);
   };
   double* drb = nullptr;
   if (resid_before) {
     drb = (double*)acs_out_buf(ctx, WS_OUT0, resid_before, res_bytes, flags);
     if (!drb) return ACS_E_NOMEM;
-    resid(b.cams, b.poses, m.pts, drb);
+    resid(b.cams, b.poses, b.pts, drb);
   }
   ExtOpts o{op.max_iters, op.ftol, op.xtol, op.gtol};
-  brd_launch_cost(s, d, b, obj, uvp, mk, 0);
-  if (n_pts > 0) ext_launch_point_cost(s, dp, b.st, 0, b.cams, m.pts, ps.uv, ps.mask, m.cid, b.Fp + n_boards);
+  brd_launch_cost(s, d, dp, b, in, 0);
   ext_launch_lm(s, de, b.st, o, 1, b.Fp, b.normp, b.camnorm);
   ACS_HIP(ctx, hipGetLastError());
-  // the iterations in groups of four (a linear chain, captured once), the status read per group
-  const int group = 4;
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t exec = nullptr;
-  bool use_graph = op.max_iters > 0 && hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed) == hipSuccess;
-  if (use_graph) {
-    for (int c = 0; c < group; ++c) bpt_enqueue(s, d, dp, de, o, m, obj, uvp, mk, ps);
-    if (hipStreamEndCapture(s, &graph) != hipSuccess ||
-        hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) {
-      if (graph) (void)hipGraphDestroy(graph);
-      (void)hipGetLastError();
-      graph = nullptr;
-      exec = nullptr;
-      use_graph = false;
-    }
-  }
-  for (int it = 0; it < op.max_iters; it += group) {
-    if (use_graph) {
-      ACS_HIP(ctx, hipGraphLaunch(exec, s));
-    } else {
-      for (int c = 0; c < group; ++c) bpt_enqueue(s, d, dp, de, o, m, obj, uvp, mk, ps);
-    }
-    ACS_HIP(ctx, hipGetLastError());
-    ACS_HIP(ctx, hipMemcpyAsync(&hs, b.st, sizeof(hs), hipMemcpyDeviceToHost, s));
-    ACS_HIP(ctx, hipStreamSynchronize(s));
-    if (hs.status != 0) break;
-  }
-  if (exec) (void)hipGraphExecDestroy(exec);
-  if (graph) (void)hipGraphDestroy(graph);
-  if (op.max_iters <= 0) {
-    ACS_HIP(ctx, hipMemcpyAsync(&hs, b.st, sizeof(hs), hipMemcpyDeviceToHost, s));
-    ACS_HIP(ctx, hipStreamSynchronize(s));
-  }
+  if ((rc = ext_lm_loop(ctx, b.st, op.max_iters, [&] { brd_enqueue(s, d, dp, de, o, b, in); }, &hs))) return rc;
   const double* fcams = b.cams + hs.cur * n_cams * ACS_CAM_STRIDE;
   const double* fposes = b.poses + (size_t)hs.cur * n_boards * 12;
-  const double* fpts = m.pts + (size_t)hs.cur * n_pts * 3;
+  const double* fpts = b.pts + (size_t)hs.cur * n_pts * 3;
   const hipMemcpyKind kout = (flags & ACS_DEVICE_PTRS) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
   if (resid_after) {
     double* dra = (double*)acs_out_buf(ctx, WS_OUT1, resid_after, res_bytes, flags);
@@ -890,6 +591,31 @@ int acs_sba_boards_points(acs_ctx* ctx, double* cams, int32_t n_cams, const doub
   ACS_HIP(ctx, hipStreamSynchronize(s));
   if (report) ext_report(report, hs, nbad);
   return ACS_OK;
+}
+
+extern "C" {
+
+int32_t acs_sba_boards_chunk(int32_t n_cams) { return brd_chunk(n_cams); }
+
+int acs_sba_boards(acs_ctx* ctx, double* cams, int32_t n_cams, const double* obj_pts, int32_t n_corners,
+                   const double* uv, const uint8_t* mask, int32_t n_boards, double* board_poses,
+                   const acs_sba_ext_opts* opts, double* resid_before, double* resid_after,
+                   acs_sba_ext_report* report, uint32_t flags) {
+  ACS_DEVICE_GUARD(ctx);
+  ACS_FISHEYE_ONLY(ctx, flags, "acs_sba_boards");
+  return brd_solve(ctx, "acs_sba_boards", cams, n_cams, obj_pts, n_corners, uv, mask, n_boards, board_poses, nullptr,
+                   nullptr, 0, nullptr, opts, resid_before, resid_after, report, flags);
+}
+
+int acs_sba_boards_points(acs_ctx* ctx, double* cams, int32_t n_cams, const double* obj_pts, int32_t n_corners,
+                          const double* uv, const uint8_t* mask, int32_t n_boards, double* board_poses,
+                          const double* pt_uv, const uint8_t* pt_mask, int32_t n_pts, double* pts,
+                          const acs_sba_ext_opts* opts, double* resid_before, double* resid_after,
+                          acs_sba_ext_report* report, uint32_t flags) {
+  ACS_DEVICE_GUARD(ctx);
+  ACS_FISHEYE_ONLY(ctx, flags, "acs_sba_boards_points");
+  return brd_solve(ctx, "acs_sba_boards_points", cams, n_cams, obj_pts, n_corners, uv, mask, n_boards, board_poses,
+                   pt_uv, pt_mask, n_pts, pts, opts, resid_before, resid_after, report, flags);
 }
 
 }  // extern "C"

@@ -25,41 +25,31 @@
 //   sigma_hat^2 = sum w r^2 / dof over the OK boards' views, dof = m - 6 n_ok - (6C - 6).
 //
 // Kernels:
-//   k_brdcov_linearize [1 block of 4 waves per board] k_brd_linearize's mapping (waves over the
-//                   cameras, lanes over the corners, group_sum<64> per entry kept by the owning
-//                   lane) without state, gradient and cost: the view record U (21), W (36) and,
-//                   over the views in camera order, V (21) and sum w r^2; then the board's
-//                   unit-diagonal LDL^T status and V^-1
+//   k_brdcov_linearize [1 block of 4 waves per board] k_brd_linearize's mapping and code (brd_stage,
+//                   brd_view_sums; sba_boards.hpp: waves over the cameras, lanes over the corners,
+//                   group_sum<64> per entry kept by the owning lane) without state, gradient and
+//                   cost: the view record U (21), W (36) and, over the views in camera order, V (21)
+//                   and sum w r^2; then the board's unit-diagonal LDL^T status and V^-1
 //   k_brdcov_schur  [board chunks x entry slices] undamped S over the OK boards: W V^-1 tiles in
-//                   LDS, each entry summed by one thread in board order (k_brd_schur's layout)
-//   k_brdcov_cams   [1 block] k_extcov_cams' algorithm with six generators and the six-row anchor
-//                   constraint: chunk sums in order, symmetrise, G and its Gram-Schmidt, mu, Jacobi
-//                   scaling, scalar pivot test, wg_spd_inverse with one refinement step, unscale,
-//                   - Q Q^T / mu, anchor transform, symmetric part, sigma^2, the report
+//                   LDS, each entry summed by one thread in board order (brd_schur_stage,
+//                   brd_schur_entry with M = V^-1: k_brd_schur's code and layout)
+//   k_brdcov_cams   [1 block] the core of sba_cov_cams.hpp with six generators (chunk sums in order,
+//                   symmetrise, Gram-Schmidt of G, mu, Jacobi scaling, scalar pivot test,
+//                   wg_spd_inverse with one refinement step, unscale, - Q Q^T / mu, the report's
+//                   sums); here G, the six-row anchor transform, the symmetric part, sigma^2, the
+//                   one-camera shortcut and the report
 //   k_brdcov_boards [4 boards per block, one wave each] cov_cc staged in LDS; lane e < 36 owns
 //                   entry e of T = sum_{c, c'} W_bc^T cov_cc[c, c'] W_bc' (seen cameras in camera
 //                   order), then V^-1 T V^-1 + sigma^2 V^-1, the upper triangle mirrored
 //   k_brdcov_board_sd [1 block] the largest board sds of the report
 // No floating-point atomics; every sum has a fixed order.
-#include "mfma64.hpp"
-#include "sba_ext.hpp"
+#include "sba_boards.hpp"
+#include "sba_cov_cams.hpp"
 
-#define BC_PIVOT_TOL 1e-9  // pivots of the unit-diagonal V_b and of the unit-diagonal reduced camera system
+#define BC_PIVOT_TOL 1e-9  // pivots of the unit-diagonal V_b
 
-// the view record per (board, camera) slot, and a view's part of the board record
-enum : int { BC_Q_U = 0, BC_Q_W = 21, BC_Q = 57 };
+// a view's part of the board record; the view record is BRD_Q<false> (sba_boards.hpp)
 enum : int { BC_P_V = 0, BC_P_WR2 = 21, BC_P = 22 };
-
-struct BcDims {
-  int B, C, nc, chunk;
-  double f2;
-};
-
-static inline int bc_nchunk(const BcDims& d) { return (d.B + d.chunk - 1) / d.chunk; }
-// LDS of a Schur block: per board W V^-1 (36 doubles per camera), V^-1, a seen flag per camera
-static inline size_t bc_schur_lds(const BcDims& d) {
-  return sizeof(double) * (size_t)d.chunk * (d.C * 36 + 36) + sizeof(int) * (size_t)d.chunk * d.C;
-}
 
 // V (packed upper, upk) -> V^-1 (row-major) through the unpivoted LDL^T of V scaled to unit
 // diagonal; false when a diagonal entry is not > 0 or a pivot fails d > BC_PIVOT_TOL (a NaN fails)
@@ -115,7 +105,7 @@ __device__ __forceinline__ bool bc_vinv(const double* V, double Vi[36]) {
   return ok;
 }
 
-__global__ __launch_bounds__(256) void k_brdcov_linearize(BcDims d, const double* __restrict__ cams,
+__global__ __launch_bounds__(256) void k_brdcov_linearize(BrdDims d, const double* __restrict__ cams,
                                                           const double* __restrict__ poses,
                                                           const double* __restrict__ obj,
                                                           const double2* __restrict__ uv,
@@ -128,75 +118,28 @@ __global__ __launch_bounds__(256) void k_brdcov_linearize(BcDims d, const double
   __shared__ double s_rp[BRD_MAXNC * 3], s_X[BRD_MAXNC * 3];
   __shared__ double s_part[EXT_MAXC][BC_P];
   __shared__ double s_v[BC_P];
-  const double* pose = poses + (size_t)b * 12;
-  for (int i = threadIdx.x; i < d.C * ACS_CAM_STRIDE; i += blockDim.x) s_cam[i] = cams[i];
-  for (int j = threadIdx.x; j < d.nc; j += blockDim.x) {
-    const double p0 = obj[3 * j], p1 = obj[3 * j + 1], p2 = obj[3 * j + 2];
-    for (int i = 0; i < 3; ++i) {
-      const double rp = pose[3 * i] * p0 + pose[3 * i + 1] * p1 + pose[3 * i + 2] * p2;
-      s_rp[3 * j + i] = rp;
-      s_X[3 * j + i] = rp + pose[9 + i];
-    }
-  }
-  __syncthreads();
+  brd_stage(d, cams, poses + (size_t)b * 12, obj, s_cam, s_rp, s_X);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = blockDim.x >> 6;
   for (int c = wave; c < d.C; c += nwave) {
     const size_t view = (size_t)b * d.C + c;
-    double* q = Qv + view * BC_Q;
+    double* q = Qv + view * BRD_Q<false>;
     if (!mask[view]) {
-      if (lane < BC_Q) q[lane] = 0.0;
+      if (lane < BRD_Q<false>) q[lane] = 0.0;
       if (lane < BC_P) s_part[c][lane] = 0.0;
       continue;
     }
-    // entry e of the 79 sums lives in lane e % 64: acc0 for e < 64, acc1 behind it
-    double acc0 = 0.0, acc1 = 0.0;
-    for (int j0 = 0; j0 < d.nc; j0 += 64) {
-      const bool live = j0 + lane < d.nc;
-      const int j = live ? j0 + lane : d.nc - 1;
-      int e = 0;
-      auto add = [&](double v) {
-        const double t = group_sum<64>(live ? v : 0.0);
-        if ((e & 63) == lane) {
-          if (e < 64)
-            acc0 += t;
-          else
-            acc1 += t;
-        }
-        ++e;
-      };
-      ExtObs ob;
-      double qo[EXT_Q<false>];
-      ext_obs_blocks(s_cam + c * ACS_CAM_STRIDE, s_X[3 * j], s_X[3 * j + 1], s_X[3 * j + 2], uv[view * d.nc + j], d.f2,
-                     ob, qo);
-      const double v0 = s_rp[3 * j], v1 = s_rp[3 * j + 1], v2 = s_rp[3 * j + 2];
-      double jb[2][6];
-#pragma unroll
-      for (int dd = 0; dd < 2; ++dd) {
-        const double* jp = ob.jp[dd];
-        jb[dd][0] = -(jp[1] * v2 - jp[2] * v1);
-        jb[dd][1] = -(jp[2] * v0 - jp[0] * v2);
-        jb[dd][2] = -(jp[0] * v1 - jp[1] * v0);
-        jb[dd][3] = jp[0];
-        jb[dd][4] = jp[1];
-        jb[dd][5] = jp[2];
-      }
-#pragma unroll
-      for (int k = 0; k < 21; ++k) add(qo[EXT_Q_U + k]);
-#pragma unroll
-      for (int i = 0; i < 6; ++i)
-#pragma unroll
-        for (int k = 0; k < 6; ++k) add(ob.wh[0] * ob.jc[0][i] * jb[0][k] + ob.wh[1] * ob.jc[1][i] * jb[1][k]);
-#pragma unroll
-      for (int i = 0; i < 6; ++i)
-#pragma unroll
-        for (int k = i; k < 6; ++k) add(ob.wh[0] * jb[0][i] * jb[0][k] + ob.wh[1] * jb[1][i] * jb[1][k]);
-      add(ob.w[0] * (ob.r[0] * ob.r[0]) + ob.w[1] * (ob.r[1] * ob.r[1]));
-    }
-    if (lane < BC_Q)
-      q[lane] = acc0;
+    // the 79 sums: nothing between W and V, then sum w r^2
+    BrdLaneSums sums{lane};
+    brd_view_sums(
+        d, s_cam + c * ACS_CAM_STRIDE, s_rp, s_X, uv + view * d.nc, sums, [](const ExtObs&, BrdLaneSums&) {},
+        [](const ExtObs& ob, const double[2][6], BrdLaneSums& add) {
+          add(ob.w[0] * (ob.r[0] * ob.r[0]) + ob.w[1] * (ob.r[1] * ob.r[1]));
+        });
+    if (lane < BRD_Q<false>)
+      q[lane] = sums.acc0;
     else
-      s_part[c][lane - BC_Q] = acc0;                                 // entries 57..63
-    if (lane < BC_P - (64 - BC_Q)) s_part[c][64 - BC_Q + lane] = acc1;  // entries 64..78
+      s_part[c][lane - BRD_Q<false>] = sums.acc0;                                    // entries 57..63
+    if (lane < BC_P - (64 - BRD_Q<false>)) s_part[c][64 - BRD_Q<false> + lane] = sums.acc1;  // entries 64..78
   }
   __syncthreads();
   if (threadIdx.x < BC_P) {
@@ -223,7 +166,7 @@ __global__ __launch_bounds__(256) void k_brdcov_linearize(BcDims d, const double
 // chunk partial of S (6C x 6C) over the OK boards of the chunk. Grid (chunks, entry slices): every
 // block stages its chunk's V^-1 and W V^-1 tiles and sums its slice of the entries, each entry by
 // one thread over the chunk's boards in order.
-__global__ __launch_bounds__(256) void k_brdcov_schur(BcDims d, const double* __restrict__ Qv,
+__global__ __launch_bounds__(256) void k_brdcov_schur(BrdDims d, const double* __restrict__ Qv,
                                                       const double* __restrict__ Vi,
                                                       const int32_t* __restrict__ status,
                                                       const uint8_t* __restrict__ mask, double* __restrict__ part) {
@@ -238,38 +181,10 @@ __global__ __launch_bounds__(256) void k_brdcov_schur(BcDims d, const double* __
   for (int i = threadIdx.x; i < nb * d.C; i += blockDim.x)
     sseen[i] = (mask[(size_t)b0 * d.C + i] && status[b0 + i / d.C] == ACS_COV_OK) ? 1 : 0;
   __syncthreads();
-  for (int i = threadIdx.x; i < nb * d.C * 36; i += blockDim.x) {
-    const int t = i / (d.C * 36), r = i % (d.C * 36), c = r / 36, k1 = (r % 36) / 6, k2 = r % 6;
-    double z = 0.0;
-    if (sseen[t * d.C + c]) {
-      const double* W = Qv + ((size_t)(b0 + t) * d.C + c) * BC_Q + BC_Q_W + k1 * 6;
-      const double* M = sM + t * 36;
-      for (int k = 0; k < 6; ++k) z += W[k] * M[k * 6 + k2];
-    }
-    sZ[i] = z;
-  }
-  __syncthreads();
+  brd_schur_stage<false>(d, b0, nb, Qv, sseen, sZ, [&](int t) -> const double* { return sM + t * 36; });
   for (int e = blockIdx.y * blockDim.x + threadIdx.x; e < nE; e += gridDim.y * blockDim.x) {
-    const int a = e / NC, bb = e % NC, c1 = a / 6, k1 = a % 6, c2 = bb / 6, k2 = bb % 6;
-    double acc = 0.0;
-    for (int t = 0; t < nb; ++t) {
-      if (!sseen[t * d.C + c1] || !sseen[t * d.C + c2]) continue;
-      const double* q1 = Qv + ((size_t)(b0 + t) * d.C + c1) * BC_Q;
-      if (c1 == c2) acc += q1[BC_Q_U + upk(k1, k2)];
-      const double* z = sZ + ((size_t)t * d.C + c1) * 36 + k1 * 6;
-      const double* w = Qv + ((size_t)(b0 + t) * d.C + c2) * BC_Q + BC_Q_W + k2 * 6;
-      double s = 0.0;
-      for (int k = 0; k < 6; ++k) s += z[k] * w[k];
-      acc -= s;
-    }
-    part[(size_t)ch * nE + e] = acc;
+    part[(size_t)ch * nE + e] = brd_schur_entry<false>(d, b0, nb, Qv, sZ, sseen, e / NC, e % NC);
   }
-}
-
-// sum over the 64 lanes of a wave, the same bits in every lane
-__device__ __forceinline__ double bc_wave_sum64(double v) {
-  for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
 }
 
 struct BcCamArgs {
@@ -277,13 +192,7 @@ struct BcCamArgs {
   double s2;
 };
 
-// LDS of k_brdcov_cams in doubles: S (NP x (NP + 1)), Q, K, MC (NP x 8 each), CM (8 x NP),
-// scale (NP), tile-inverse scratch (512), reductions (256), small (128), the report's counts (1024)
-static size_t bc_cams_lds(int NP) {
-  return sizeof(double) * ((size_t)NP * (NP + 1) + 4 * (size_t)NP * 8 + NP + 512 + 256 + 128 + 1024);
-}
-
-__global__ __launch_bounds__(256) void k_brdcov_cams(BcDims d, BcCamArgs ar, const double* __restrict__ part,
+__global__ __launch_bounds__(256) void k_brdcov_cams(BrdDims d, BcCamArgs ar, const double* __restrict__ part,
                                                      const double* __restrict__ cams,
                                                      const int32_t* __restrict__ status,
                                                      const double* __restrict__ wr2, const int32_t* __restrict__ nres,
@@ -294,32 +203,16 @@ __global__ __launch_bounds__(256) void k_brdcov_cams(BcDims d, BcCamArgs ar, con
   const int NC = 6 * d.C, NP = ((NC + 15) / 16) * 16, LD = NP + 1, nE = NC * NC;
   const int tid = threadIdx.x;
   extern __shared__ double lds[];
-  double* sS = lds;               // NP x LD
-  double* sQ = sS + NP * LD;      // NP x 8: G, then its orthonormal basis (six columns)
-  double* sK = sQ + NP * 8;       // NP x 8: Q (Cm Q)^-1
-  double* sMC = sK + NP * 8;      // NP x 8: M Cm^T
-  double* sCM = sMC + NP * 8;     // 8 x NP: Cm M
-  double* ssc = sCM + 8 * NP;     // NP: Jacobi scaling
-  double* tmp = ssc + NP;         // 512
-  double* s_red = tmp + 512;      // 256
-  double* s_sm = s_red + 256;     // 128: [0] gauge rank flag, [1] mu, [2] anchor flag, 16.. (Cm Q)^-1, 56.. its Gauss-Jordan tableau
+  const CovCamsLds L = cov_cams_carve(lds, NP);
+  // sQ: six columns; s_sm: from 16 (Cm Q)^-1, from 56 its Gauss-Jordan tableau
+  double *sS = L.sS, *sQ = L.sQ, *sK = L.sK, *sMC = L.sMC, *sCM = L.sCM, *s_sm = L.s_sm;
   const bool single = d.C == 1;   // one camera is pure gauge: nothing is formed or factored
   const bool anchored = ar.gauge == ACS_GAUGE_ANCHOR;
   const double nan = __builtin_nan("");
   double minp = single ? nan : __builtin_inf();
   bool degenerate = false, gbad = false;  // uniform
   if (!single) {
-    // 1. chunk sums in order (raw S to T1), then the symmetrised S to LDS
-    for (int e = tid; e < nE; e += blockDim.x) {
-      double v = 0.0;
-      for (int ch = 0; ch < ar.nchunk; ++ch) v += part[(size_t)ch * nE + e];
-      T1[e] = v;
-    }
-    __syncthreads();
-    for (int e = tid; e < NP * NP; e += blockDim.x) {
-      const int r = e / NP, c = e % NP;
-      sS[r * LD + c] = (r < NC && c < NC) ? 0.5 * (T1[r * NC + c] + T1[c * NC + r]) : 0.0;
-    }
+    cov_cams_sum_chunks(L, NC, NP, ar.nchunk, part, T1);  // 1.
     // 2. gauge generators
     for (int e = tid; e < NP * 8; e += blockDim.x) {
       const int r = e >> 3, k = e & 7;
@@ -335,106 +228,10 @@ __global__ __launch_bounds__(256) void k_brdcov_cams(BcDims d, BcCamArgs ar, con
       sQ[e] = v;
     }
     __syncthreads();
-    // 3. wave 0: two-pass Gram-Schmidt (lane l owns rows l and l + 64) and mu = max diag S
-    if (tid < 64) {
-      const int r0 = tid, r1 = tid + 64;
-      const bool h0 = r0 < NC, h1 = r1 < NC;  // rows past NC are not this lane's to touch
-      int gb = 0;
-      for (int k = 0; k < 6; ++k) {
-        double x0 = h0 ? sQ[r0 * 8 + k] : 0.0, x1 = h1 ? sQ[r1 * 8 + k] : 0.0;
-        const double n0 = sqrt(bc_wave_sum64(x0 * x0 + x1 * x1));
-        for (int pass = 0; pass < 2; ++pass)
-          for (int j = 0; j < k; ++j) {
-            const double q0 = h0 ? sQ[r0 * 8 + j] : 0.0, q1 = h1 ? sQ[r1 * 8 + j] : 0.0;
-            const double dot = bc_wave_sum64(q0 * x0 + q1 * x1);
-            x0 -= dot * q0;
-            x1 -= dot * q1;
-          }
-        const double n1 = sqrt(bc_wave_sum64(x0 * x0 + x1 * x1));
-        const bool ok = n1 > 1e-8 * n0;  // a column in the span of the earlier ones: rank < 6
-        const double inv = ok ? 1.0 / n1 : 0.0;
-        gb |= ok ? 0 : 1;
-        if (h0) sQ[r0 * 8 + k] = x0 * inv;
-        if (h1) sQ[r1 * 8 + k] = x1 * inv;
-      }
-      double mu = h0 ? sS[r0 * LD + r0] : 0.0;
-      if (h1) mu = fmax(mu, sS[r1 * LD + r1]);
-      for (int m = 32; m > 0; m >>= 1) mu = fmax(mu, __shfl_xor(mu, m, 64));
-      if (tid == 0) {
-        s_sm[0] = (double)gb;
-        s_sm[1] = mu > 0.0 ? mu : 1.0;
-        s_sm[2] = 0.0;
-      }
-    }
-    __syncthreads();
-    const double mu = s_sm[1];
-    // 4. A = S + mu Q Q^T, scaled to unit diagonal (a diagonal entry that is not > 0 zeroes its row
-    //    and column, which the pivot test then fails)
-    for (int r = tid; r < NP; r += blockDim.x) {
-      double sc = 1.0;
-      if (r < NC) {
-        double qq = 0.0;
-        for (int k = 0; k < 6; ++k) qq += sQ[r * 8 + k] * sQ[r * 8 + k];
-        const double dd = sS[r * LD + r] + mu * qq;
-        sc = dd > 0.0 ? 1.0 / sqrt(dd) : 0.0;
-      }
-      ssc[r] = sc;
-    }
-    __syncthreads();
-    for (int e = tid; e < NP * NP; e += blockDim.x) {
-      const int r = e / NP, c = e % NP;
-      double v = r == c ? 1.0 : 0.0;
-      if (r < NC && c < NC) {
-        double qq = 0.0;
-        for (int k = 0; k < 6; ++k) qq += sQ[r * 8 + k] * sQ[c * 8 + k];
-        v = (sS[r * LD + c] + mu * qq) * ssc[r] * ssc[c];
-      }
-      sS[r * LD + c] = v;
-      Ag[e] = v;  // kept for the inverse and its refinement
-    }
-    __syncthreads();
-    // 5. pivot test: scalar right-looking LDL^T of Ah in natural order, in place (Ah is reloaded)
-    bool pbad = false;
-    for (int k = 0; k < NC; ++k) {
-      const double dk = sS[k * LD + k];  // uniform
-      if (!(dk > BC_PIVOT_TOL)) {        // a NaN fails
-        pbad = true;
-        minp = dk < minp ? dk : (dk != dk ? dk : minp);
-        break;
-      }
-      minp = fmin(minp, dk);
-      const double inv = 1.0 / dk;
-      const int m = NC - k - 1;
-      for (int e = tid; e < m * m; e += blockDim.x) {
-        const int i = k + 1 + e / m, j = k + 1 + e % m;
-        sS[i * LD + j] -= sS[i * LD + k] * inv * sS[k * LD + j];
-      }
-      __syncthreads();
-    }
-    __syncthreads();
-    gbad = s_sm[0] != 0.0;
-    degenerate = pbad || gbad;
+    double mu;
+    degenerate = cov_cams_factor<6>(L, NC, NP, Ag, mu, minp, gbad);  // 3. - 5.
     if (!degenerate) {
-      // 6. SPD inverse on the MFMA tiles
-      for (int e = tid; e < NP * NP; e += blockDim.x) sS[(e / NP) * LD + e % NP] = Ag[e];
-      __syncthreads();
-      wg_spd_inverse(sS, LD, NP >> 4, tmp, bad);
-      // 7. one refinement step X <- X + X (I - Ah X)
-      wg_mgemm<false, false>(T1, NP, Ag, NP, sS, LD, NP, NP, NP, -1.0, 0.0);
-      for (int r = tid; r < NP; r += blockDim.x) T1[r * NP + r] += 1.0;
-      __syncthreads();
-      wg_mgemm<false, false>(T2, NP, sS, LD, T1, NP, NP, NP, NP, 1.0, 0.0);
-      for (int e = tid; e < NP * NP; e += blockDim.x) sS[(e / NP) * LD + e % NP] += T2[e];
-      __syncthreads();
-      // 8. unscale, minus Q Q^T / mu
-      const double imu = 1.0 / mu;
-      for (int e = tid; e < nE; e += blockDim.x) {
-        const int r = e / NC, c = e % NC;
-        double qq = 0.0;
-        for (int k = 0; k < 6; ++k) qq += sQ[r * 8 + k] * sQ[c * 8 + k];
-        sS[r * LD + c] = sS[r * LD + c] * ssc[r] * ssc[c] - qq * imu;
-      }
-      __syncthreads();
+      cov_cams_invert<6>(L, NC, NP, mu, Ag, T1, T2, bad);  // 6. - 8.
       if (anchored) {
         // 9. M <- P M P^T, P = I - K Cm, K = Q (Cm Q)^-1, Cm the identity on camera a
         if (tid == 0) {
@@ -521,55 +318,20 @@ __global__ __launch_bounds__(256) void k_brdcov_cams(BcDims d, BcCamArgs ar, con
     if (single || (anchored && (r / 6 == ar.a || c / 6 == ar.a))) v = 0.0;
     cov[e] = degenerate ? nan : v;
   }
-  // the report: sd extremes and the board sums, fixed-order trees
-  double rs = 0.0, ts = 0.0, sw = 0.0;
-  long long cnt[3] = {0, 0, 0}, m = 0;
-  for (int r = tid; r < NC; r += blockDim.x) {
-    double v = ar.s2 * sS[r * LD + r];
-    if (single || (anchored && r / 6 == ar.a)) v = 0.0;
-    const double sd = sqrt(v);
-    if (r % 6 < 3)
-      rs = fmax(rs, sd);
-    else
-      ts = fmax(ts, sd);
-  }
-  for (int i = tid; i < d.B; i += blockDim.x) {
-    const int s = status[i];
-    if (s >= 0 && s < 3) cnt[s]++;
-    sw += wr2[i];
-    m += nres[i];
-  }
-  __syncthreads();
-  double* rd = tmp;                         // 256 x 2: sum w r^2 and the rotation sd maximum
-  long long* ri = (long long*)(s_sm + 128);  // 256 x 4
-  rd[tid] = sw;
-  rd[256 + tid] = rs;
-  s_red[tid] = ts;
-  for (int k = 0; k < 3; ++k) ri[tid * 4 + k] = cnt[k];
-  ri[tid * 4 + 3] = m;
-  __syncthreads();
-  for (int h = 128; h > 0; h >>= 1) {
-    if (tid < h) {
-      rd[tid] += rd[tid + h];
-      rd[256 + tid] = fmax(rd[256 + tid], rd[256 + tid + h]);
-      s_red[tid] = fmax(s_red[tid], s_red[tid + h]);
-      for (int k = 0; k < 4; ++k) ri[tid * 4 + k] += ri[(tid + h) * 4 + k];
-    }
-    __syncthreads();
-  }
+  const CovCamsTotals tot = cov_cams_totals(L, NC, NP, ar.s2, anchored ? ar.a : -1, single, d.B, status, wr2, nres);
   if (tid == 0) {
-    const long long n_ok = ri[0], dof = ri[3] - 6 * n_ok - (6 * d.C - 6);
+    const long long n_ok = tot.n_ok, dof = tot.n_res - 6 * n_ok - (6 * d.C - 6);
     rep->status = degenerate ? ACS_EXT_COV_DEGENERATE : ACS_EXT_COV_OK;
     rep->reserved = 0;
     rep->n_boards = d.B;
     rep->n_ok = n_ok;
-    rep->n_noobs = ri[1];
-    rep->n_degenerate = ri[2];
+    rep->n_noobs = tot.n_noobs;
+    rep->n_degenerate = tot.n_degenerate;
     rep->dof = dof;
     rep->min_pivot = gbad ? 0.0 : minp;
-    rep->sigma_hat_px = dof > 0 ? sqrt(rd[0] / (double)dof) : nan;
-    rep->rot_sd_max = degenerate ? nan : rd[256];
-    rep->trans_sd_max = degenerate ? nan : s_red[0];
+    rep->sigma_hat_px = dof > 0 ? sqrt(tot.wr2 / (double)dof) : nan;
+    rep->rot_sd_max = degenerate ? nan : tot.rot_sd_max;
+    rep->trans_sd_max = degenerate ? nan : tot.trans_sd_max;
     rep->board_rot_sd_max = nan;  // k_brdcov_board_sd
     rep->board_trans_sd_max = nan;
   }
@@ -577,7 +339,7 @@ __global__ __launch_bounds__(256) void k_brdcov_cams(BcDims d, BcCamArgs ar, con
 
 // One wave per board, four boards per block. cov_cc (6C x 6C, sigma^2 applied) is staged in LDS
 // (dynamic, behind four 36-double T tiles); lane e < 36 owns entry (e / 6, e % 6).
-__global__ __launch_bounds__(256) void k_brdcov_boards(BcDims d, const double* __restrict__ covc,
+__global__ __launch_bounds__(256) void k_brdcov_boards(BrdDims d, const double* __restrict__ covc,
                                                        const double* __restrict__ Qv, const double* __restrict__ Vi,
                                                        const int32_t* __restrict__ status,
                                                        const uint8_t* __restrict__ mask, double s2,
@@ -597,13 +359,13 @@ __global__ __launch_bounds__(256) void k_brdcov_boards(BcDims d, const double* _
   double acc = 0.0;
   if (bok) {
     const uint8_t* mk = mask + (size_t)b * d.C;
-    const double* Wb = Qv + (size_t)b * d.C * BC_Q + BC_Q_W;
+    const double* Wb = Qv + (size_t)b * d.C * BRD_Q<false> + BRD_Q_W;
     for (int c1 = 0; c1 < d.C; ++c1) {
       if (!mk[c1]) continue;
-      const double* W1 = Wb + (size_t)c1 * BC_Q;
+      const double* W1 = Wb + (size_t)c1 * BRD_Q<false>;
       for (int c2 = 0; c2 < d.C; ++c2) {
         if (!mk[c2]) continue;
-        const double* W2 = Wb + (size_t)c2 * BC_Q;
+        const double* W2 = Wb + (size_t)c2 * BRD_Q<false>;
         const double* blk = s_cc + (size_t)(6 * c1) * NC + 6 * c2;
         for (int k = 0; k < 6; ++k) {
           double s = 0.0;
@@ -632,7 +394,7 @@ __global__ __launch_bounds__(256) void k_brdcov_boards(BcDims d, const double* _
 }
 
 // the largest rotation and translation sd over the OK boards (a maximum: any order gives the same bits)
-__global__ __launch_bounds__(256) void k_brdcov_board_sd(BcDims d, const double* __restrict__ covb,
+__global__ __launch_bounds__(256) void k_brdcov_board_sd(BrdDims d, const double* __restrict__ covb,
                                                          const int32_t* __restrict__ status,
                                                          acs_sba_boards_cov_report* __restrict__ rep) {
   __shared__ double s_r[256], s_t[256];
@@ -689,7 +451,7 @@ int acs_sba_boards_covariance(acs_ctx* ctx, const double* cams, int32_t n_cams, 
               op.anchor_cam, n_cams - 1);
   ACS_CHECK(ctx, cams && obj_pts && uv && mask && board_poses && cov_cams, "acs_sba_boards_covariance: null argument");
   hipStream_t s = ctx->stream;
-  const BcDims d{n_boards, n_cams, n_corners, acs_sba_boards_chunk(n_cams), op.f_scale * op.f_scale};
+  const BrdDims d = brd_dims(n_boards, n_cams, n_corners, op.f_scale);
   const size_t views = (size_t)n_boards * n_cams;
   int rc;
   void *dcams, *dobj, *duv, *dmask, *dposes;
@@ -699,14 +461,14 @@ int acs_sba_boards_covariance(acs_ctx* ctx, const double* cams, int32_t n_cams, 
   if ((rc = acs_stage_in(ctx, WS_MASK, mask, views, flags, &dmask))) return rc;
   if ((rc = acs_stage_in(ctx, WS_TMP0, board_poses, sizeof(double) * 12 * n_boards, flags, &dposes))) return rc;
   const uint8_t* mk = (const uint8_t*)dmask;
-  const int nchunk = bc_nchunk(d);
+  const int nchunk = brd_nchunk(d);
   const int NC = 6 * n_cams, NP = ((NC + 15) / 16) * 16, nE = NC * NC;
   double *Qv, *Vi, *wr2, *part, *Ag, *T1, *T2;
   int32_t* nres;
   int* bad;
   auto layout = [&](double* base) {
     Arena a{base};
-    Qv = a.take(views * BC_Q);
+    Qv = a.take(views * BRD_Q<false>);
     Vi = a.take((size_t)n_boards * 36);
     wr2 = a.take(n_boards);
     nres = a.take<int32_t>(((size_t)n_boards + 1) / 2);
@@ -733,10 +495,10 @@ int acs_sba_boards_covariance(acs_ctx* ctx, const double* cams, int32_t n_cams, 
                      (const double*)dposes, (const double*)dobj, (const double2*)duv, mk, Qv, Vi, dst, wr2, nres);
   if (n_cams > 1) {
     const int nslice = acs_grid(nE, 256);  // one entry per thread
-    hipLaunchKernelGGL(k_brdcov_schur, dim3(nchunk, nslice), dim3(256), bc_schur_lds(d), s, d, Qv, Vi, dst, mk, part);
+    hipLaunchKernelGGL(k_brdcov_schur, dim3(nchunk, nslice), dim3(256), brd_schur_lds(d, 36), s, d, Qv, Vi, dst, mk, part);
   }
   BcCamArgs ar{nchunk, op.gauge, anchored ? op.anchor_cam : 0, 0, op.sigma_px * op.sigma_px};
-  hipLaunchKernelGGL(k_brdcov_cams, dim3(1), dim3(256), bc_cams_lds(NP), s, d, ar, part, (const double*)dcams, dst, wr2,
+  hipLaunchKernelGGL(k_brdcov_cams, dim3(1), dim3(256), cov_cams_lds(NP), s, d, ar, part, (const double*)dcams, dst, wr2,
                      nres, Ag, T1, T2, dcc, drep, bad);
   hipLaunchKernelGGL(k_brdcov_boards, dim3(acs_grid(n_boards, 4)), dim3(256), sizeof(double) * (144 + nE), s, d, dcc, Qv,
                      Vi, dst, mk, ar.s2, drep, dcb);

@@ -19,6 +19,8 @@
 //   k_ext_cam       [1 block] trial cameras R <- exp([dw]x) R, t <- t + dt
 //   k_ext_cost      [point groups] robust cost at the trial state
 //   k_ext_lm        [1 block] accept / reject, lambda, stop tests
+// The iterations run in ext_lm_loop (groups of four, captured once), which the rigid-board solves
+// (sba_boards.hip) drive with their own iteration.
 // In a multi-GPU run the per-rank partial (S, b) is what one all-reduce would sum.
 #include <algorithm>
 
@@ -548,6 +550,46 @@ void ext_report(acs_sba_ext_report* report, const ExtState& hs, int nbad) {
   report->lambda_final = hs.lam;
 }
 
+// the iterations in groups of four (a linear chain, captured once), the status read per group.
+// Every decision counts an iteration or stops, so max_iters of them end the solve: no replay beyond
+// them, and none at all for max_iters <= 0 (the state comes back as it went in)
+int ext_lm_loop(acs_ctx* ctx, const ExtState* st, int max_iters, const std::function<void()>& enqueue, ExtState* hs) {
+  hipStream_t s = ctx->stream;
+  const int group = 4;
+  hipGraph_t graph = nullptr;
+  hipGraphExec_t exec = nullptr;
+  bool use_graph = max_iters > 0 && hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed) == hipSuccess;
+  if (use_graph) {
+    for (int c = 0; c < group; ++c) enqueue();
+    if (hipStreamEndCapture(s, &graph) != hipSuccess ||
+        hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) {
+      if (graph) (void)hipGraphDestroy(graph);
+      (void)hipGetLastError();
+      graph = nullptr;
+      exec = nullptr;
+      use_graph = false;
+    }
+  }
+  for (int it = 0; it < max_iters; it += group) {
+    if (use_graph) {
+      ACS_HIP(ctx, hipGraphLaunch(exec, s));
+    } else {
+      for (int c = 0; c < group; ++c) enqueue();
+    }
+    ACS_HIP(ctx, hipGetLastError());
+    ACS_HIP(ctx, hipMemcpyAsync(hs, st, sizeof(*hs), hipMemcpyDeviceToHost, s));
+    ACS_HIP(ctx, hipStreamSynchronize(s));
+    if (hs->status != 0) break;
+  }
+  if (exec) (void)hipGraphExecDestroy(exec);
+  if (graph) (void)hipGraphDestroy(graph);
+  if (max_iters <= 0) {
+    ACS_HIP(ctx, hipMemcpyAsync(hs, st, sizeof(*hs), hipMemcpyDeviceToHost, s));
+    ACS_HIP(ctx, hipStreamSynchronize(s));
+  }
+  return ACS_OK;
+}
+
 extern "C" {
 
 void acs_sba_ext_default_opts(acs_sba_ext_opts* o) {
@@ -609,42 +651,8 @@ int acs_sba_extrinsics(acs_ctx* ctx, double* cams, int32_t n_cams, const double*
   ext_launch_cost(s, d, b, 0);
   ext_launch_lm(s, d, b.st, o, 1, b.Fp, b.normp, b.camnorm);
   ACS_HIP(ctx, hipGetLastError());
-  const int chunk = 4;
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t exec = nullptr;
-  bool use_graph = op.max_iters > 0 && hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed) == hipSuccess;
-  if (use_graph) {
-    for (int c = 0; c < chunk; ++c) ext_enqueue(s, d, o, b);
-    if (hipStreamEndCapture(s, &graph) != hipSuccess ||
-        hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) {
-      if (graph) (void)hipGraphDestroy(graph);
-      (void)hipGetLastError();
-      graph = nullptr;
-      exec = nullptr;
-      use_graph = false;
-    }
-  }
   ExtState hs;
-  std::memset(&hs, 0, sizeof(hs));
-  // every decision counts an iteration or stops, so max_iters of them end the solve: no replay
-  // beyond them, and none at all for max_iters = 0 (the state comes back as it went in)
-  for (int it = 0; it < op.max_iters; it += chunk) {
-    if (use_graph) {
-      ACS_HIP(ctx, hipGraphLaunch(exec, s));
-    } else {
-      for (int c = 0; c < chunk; ++c) ext_enqueue(s, d, o, b);
-    }
-    ACS_HIP(ctx, hipGetLastError());
-    ACS_HIP(ctx, hipMemcpyAsync(&hs, b.st, sizeof(hs), hipMemcpyDeviceToHost, s));
-    ACS_HIP(ctx, hipStreamSynchronize(s));
-    if (hs.status != 0) break;
-  }
-  if (exec) (void)hipGraphExecDestroy(exec);
-  if (graph) (void)hipGraphDestroy(graph);
-  if (op.max_iters == 0) {
-    ACS_HIP(ctx, hipMemcpyAsync(&hs, b.st, sizeof(hs), hipMemcpyDeviceToHost, s));
-    ACS_HIP(ctx, hipStreamSynchronize(s));
-  }
+  if ((rc = ext_lm_loop(ctx, b.st, op.max_iters, [&] { ext_enqueue(s, d, o, b); }, &hs))) return rc;
   const double* fcams = b.cams + hs.cur * n_cams * ACS_CAM_STRIDE;
   const double* fpts = b.pts + (size_t)hs.cur * n_pts * 3;
   const hipMemcpyKind kout = (flags & ACS_DEVICE_PTRS) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;

@@ -1,11 +1,14 @@
 // sba_ext.hpp — what the points + extrinsics SBA (sba_ext.hip) and its covariance
 // (sba_ext_cov.hip) share: the problem's dimensions, the slot record, an observation's blocks
 // (ext_obs_blocks) and the Schur partials (ext_schur_stage, ext_schur_entry); and what the
-// rigid-board SBA (sba_boards.hip) takes from the solver: the LM state and options, the launches
-// of k_ext_solve / k_ext_cam / k_ext_lm and the exponential map (EXT_EXP_SO3).
+// rigid-board SBA (sba_boards.hip, through sba_boards.hpp) takes from the solver: the LM state and
+// options, the driver loop (ext_lm_loop), the launches of k_ext_solve / k_ext_cam / k_ext_lm and of
+// the point side, and the exponential map (EXT_EXP_SO3). The reduced-camera covariance core the two
+// covariances share is in sba_cov_cams.hpp.
 #pragma once
 
 #include <algorithm>
+#include <functional>
 
 #include "common.hpp"
 
@@ -73,6 +76,13 @@ void ext_launch_cam(hipStream_t s, const ExtDims& d, const ExtState* st, const d
 void ext_launch_lm(hipStream_t s, const ExtDims& d, ExtState* st, const ExtOpts& o, int init, const double* Fp,
                    const double* normp, const double* camnorm);
 void ext_report(acs_sba_ext_report* report, const ExtState& hs, int nbad);
+
+// The LM driver loop of a single-GPU solve (acs_sba_extrinsics, the board solves): the iterations
+// that enqueue() puts on the context's stream, in groups of four captured once into a graph (plain
+// launches when capture or instantiation fails), the device state st read into *hs after every
+// group, until a status is set or max_iters decisions are through. No iteration for max_iters <= 0:
+// *hs is then the state as it stands. An ACS_* code.
+int ext_lm_loop(acs_ctx* ctx, const ExtState* st, int max_iters, const std::function<void()>& enqueue, ExtState* hs);
 
 // The point side, for the rigid-board SBA with free points (acs_sba_boards_points): k_ext_linearize,
 // k_ext_schur (ext_nchunk(d) partials from part), k_ext_back and k_ext_cost as they are, on the

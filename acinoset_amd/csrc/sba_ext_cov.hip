@@ -21,16 +21,16 @@
 //                   the sigma_hat terms
 //   k_extcov_schur  [point chunks] fixed-order chunk partials of S over the OK points
 //                   (ext_schur_stage, ext_schur_entry with M = V^-1; no atomics)
-//   k_extcov_cams   [1 block] chunk sums in order, symmetrise, G and its Gram-Schmidt, mu,
-//                   Jacobi scaling, scalar LDL^T pivot test, SPD inverse on the f64 MFMA tiles
-//                   (wg_spd_inverse) with one refinement step, unscale, - Q Q^T / mu, anchor
-//                   transform, mirror, sigma^2, the report
+//   k_extcov_cams   [1 block] the core of sba_cov_cams.hpp with seven generators (chunk sums in
+//                   order, symmetrise, Gram-Schmidt of G, mu, Jacobi scaling, scalar LDL^T pivot
+//                   test, SPD inverse on the f64 MFMA tiles (wg_spd_inverse) with one refinement
+//                   step, unscale, - Q Q^T / mu, the report's sums; shared with k_brdcov_cams of
+//                   sba_boards_cov.hip); here G, the anchor transform with the baseline row, the
+//                   mirror, sigma^2 and the report
 //   k_extcov_points<G> [point groups] cov_cc staged in LDS; lane l owns slot l: T = sum_o'
 //                   cov_cc[c_o, c_o'] W_o', then W_o^T T, group_sum, lane 0 writes the record
-#include "mfma64.hpp"
+#include "sba_cov_cams.hpp"
 #include "sba_ext.hpp"
-
-#define XC_PIVOT_TOL 1e-9  // pivots of the unit-diagonal reduced camera system (k_extcov_cams)
 
 template <int G>
 __global__ __launch_bounds__(256) void k_extcov_linearize(ExtDims d, const double* __restrict__ cams,
@@ -110,22 +110,10 @@ __global__ __launch_bounds__(256) void k_extcov_schur(ExtDims d, const double* _
     part[(size_t)ch * nE + e] = ext_schur_entry<false>(d, p0, np, Q, sZ, scam, e / NC, e % NC);
 }
 
-// sum over the 64 lanes of a wave, the same bits in every lane
-__device__ __forceinline__ double wave_sum64(double v) {
-  for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
 struct XcCamArgs {
   int nchunk, gauge, a, b;
   double s2;
 };
-
-// LDS of k_extcov_cams in doubles: S (NP x (NP + 1)), Q, K, MC (NP x 8 each), CM (8 x NP),
-// scale (NP), tile-inverse scratch (512), reductions (256), small (128), the report's counts (1024)
-static size_t extcov_cams_lds(int NP) {
-  return sizeof(double) * ((size_t)NP * (NP + 1) + 4 * (size_t)NP * 8 + NP + 512 + 256 + 128 + 1024);
-}
 
 __global__ __launch_bounds__(256) void k_extcov_cams(ExtDims d, XcCamArgs ar, const double* __restrict__ part,
                                                      const double* __restrict__ cams,
@@ -137,26 +125,10 @@ __global__ __launch_bounds__(256) void k_extcov_cams(ExtDims d, XcCamArgs ar, co
   const int NC = 6 * d.C, NP = ((NC + 15) / 16) * 16, LD = NP + 1, nE = NC * NC;
   const int tid = threadIdx.x;
   extern __shared__ double lds[];
-  double* sS = lds;               // NP x LD
-  double* sQ = sS + NP * LD;      // NP x 8: G, then its orthonormal basis
-  double* sK = sQ + NP * 8;       // NP x 8: Q (Cm Q)^-1
-  double* sMC = sK + NP * 8;      // NP x 8: M Cm^T
-  double* sCM = sMC + NP * 8;     // 8 x NP: Cm M
-  double* ssc = sCM + 8 * NP;     // NP: Jacobi scaling
-  double* tmp = ssc + NP;         // 512
-  double* s_red = tmp + 512;      // 256
-  double* s_sm = s_red + 256;     // 128: [0] gauge rank flag, [1] mu, [2] anchor flag, 8.. h, 16.. (Cm Q)^-1
-  // 1. chunk sums in order (raw S to T1), then the symmetrised S to LDS
-  for (int e = tid; e < nE; e += blockDim.x) {
-    double v = 0.0;
-    for (int ch = 0; ch < ar.nchunk; ++ch) v += part[(size_t)ch * nE + e];
-    T1[e] = v;
-  }
-  __syncthreads();
-  for (int e = tid; e < NP * NP; e += blockDim.x) {
-    const int r = e / NP, c = e % NP;
-    sS[r * LD + c] = (r < NC && c < NC) ? 0.5 * (T1[r * NC + c] + T1[c * NC + r]) : 0.0;
-  }
+  const CovCamsLds L = cov_cams_carve(lds, NP);
+  // sQ: seven columns; s_sm: from 8 h, from 16 (Cm Q)^-1
+  double *sS = L.sS, *sQ = L.sQ, *sK = L.sK, *sMC = L.sMC, *sCM = L.sCM, *s_sm = L.s_sm;
+  cov_cams_sum_chunks(L, NC, NP, ar.nchunk, part, T1);  // 1.
   // 2. gauge generators
   for (int e = tid; e < NP * 8; e += blockDim.x) {
     const int r = e >> 3, k = e & 7;
@@ -172,107 +144,11 @@ __global__ __launch_bounds__(256) void k_extcov_cams(ExtDims d, XcCamArgs ar, co
     sQ[e] = v;
   }
   __syncthreads();
-  // 3. wave 0: two-pass Gram-Schmidt (lane l owns rows l and l + 64) and mu = max diag S
-  if (tid < 64) {
-    const int r0 = tid, r1 = tid + 64;
-    const bool h0 = r0 < NC, h1 = r1 < NC;  // rows past NC are not this lane's to touch
-    int gbad = 0;
-    for (int k = 0; k < 7; ++k) {
-      double x0 = h0 ? sQ[r0 * 8 + k] : 0.0, x1 = h1 ? sQ[r1 * 8 + k] : 0.0;
-      const double n0 = sqrt(wave_sum64(x0 * x0 + x1 * x1));
-      for (int pass = 0; pass < 2; ++pass)
-        for (int j = 0; j < k; ++j) {
-          const double q0 = h0 ? sQ[r0 * 8 + j] : 0.0, q1 = h1 ? sQ[r1 * 8 + j] : 0.0;
-          const double dot = wave_sum64(q0 * x0 + q1 * x1);
-          x0 -= dot * q0;
-          x1 -= dot * q1;
-        }
-      const double n1 = sqrt(wave_sum64(x0 * x0 + x1 * x1));
-      const bool ok = n1 > 1e-8 * n0;  // a column in the span of the earlier ones: rank < 7
-      const double inv = ok ? 1.0 / n1 : 0.0;
-      gbad |= ok ? 0 : 1;
-      if (h0) sQ[r0 * 8 + k] = x0 * inv;
-      if (h1) sQ[r1 * 8 + k] = x1 * inv;
-    }
-    double mu = h0 ? sS[r0 * LD + r0] : 0.0;
-    if (h1) mu = fmax(mu, sS[r1 * LD + r1]);
-    for (int m = 32; m > 0; m >>= 1) mu = fmax(mu, __shfl_xor(mu, m, 64));
-    if (tid == 0) {
-      s_sm[0] = (double)gbad;
-      s_sm[1] = mu > 0.0 ? mu : 1.0;
-      s_sm[2] = 0.0;
-    }
-  }
-  __syncthreads();
-  const double mu = s_sm[1];
-  // 4. A = S + mu Q Q^T, scaled to unit diagonal (a diagonal entry that is not > 0 zeroes its row
-  //    and column, which the pivot test then fails)
-  for (int r = tid; r < NP; r += blockDim.x) {
-    double sc = 1.0;
-    if (r < NC) {
-      double qq = 0.0;
-      for (int k = 0; k < 7; ++k) qq += sQ[r * 8 + k] * sQ[r * 8 + k];
-      const double dd = sS[r * LD + r] + mu * qq;
-      sc = dd > 0.0 ? 1.0 / sqrt(dd) : 0.0;
-    }
-    ssc[r] = sc;
-  }
-  __syncthreads();
-  for (int e = tid; e < NP * NP; e += blockDim.x) {
-    const int r = e / NP, c = e % NP;
-    double v = r == c ? 1.0 : 0.0;
-    if (r < NC && c < NC) {
-      double qq = 0.0;
-      for (int k = 0; k < 7; ++k) qq += sQ[r * 8 + k] * sQ[c * 8 + k];
-      v = (sS[r * LD + c] + mu * qq) * ssc[r] * ssc[c];
-    }
-    sS[r * LD + c] = v;
-    Ag[e] = v;  // kept for the inverse and its refinement
-  }
-  __syncthreads();
-  // 5. pivot test: scalar right-looking LDL^T of Ah in natural order, in place (Ah is reloaded)
-  double minp = __builtin_inf();
-  bool pbad = false;
-  for (int k = 0; k < NC; ++k) {
-    const double dk = sS[k * LD + k];  // uniform
-    if (!(dk > XC_PIVOT_TOL)) {        // a NaN fails
-      pbad = true;
-      minp = dk < minp ? dk : (dk != dk ? dk : minp);
-      break;
-    }
-    minp = fmin(minp, dk);
-    const double inv = 1.0 / dk;
-    const int m = NC - k - 1;
-    for (int e = tid; e < m * m; e += blockDim.x) {
-      const int i = k + 1 + e / m, j = k + 1 + e % m;
-      sS[i * LD + j] -= sS[i * LD + k] * inv * sS[k * LD + j];
-    }
-    __syncthreads();
-  }
-  __syncthreads();
-  const bool gbad = s_sm[0] != 0.0;
-  bool degenerate = pbad || gbad;  // uniform
+  double mu, minp = __builtin_inf();
+  bool gbad;
+  bool degenerate = cov_cams_factor<7>(L, NC, NP, Ag, mu, minp, gbad);  // 3. - 5., uniform
   if (!degenerate) {
-    // 6. SPD inverse on the MFMA tiles
-    for (int e = tid; e < NP * NP; e += blockDim.x) sS[(e / NP) * LD + e % NP] = Ag[e];
-    __syncthreads();
-    wg_spd_inverse(sS, LD, NP >> 4, tmp, bad);
-    // 7. one refinement step X <- X + X (I - Ah X)
-    wg_mgemm<false, false>(T1, NP, Ag, NP, sS, LD, NP, NP, NP, -1.0, 0.0);
-    for (int r = tid; r < NP; r += blockDim.x) T1[r * NP + r] += 1.0;
-    __syncthreads();
-    wg_mgemm<false, false>(T2, NP, sS, LD, T1, NP, NP, NP, NP, 1.0, 0.0);
-    for (int e = tid; e < NP * NP; e += blockDim.x) sS[(e / NP) * LD + e % NP] += T2[e];
-    __syncthreads();
-    // 8. unscale, minus Q Q^T / mu
-    const double imu = 1.0 / mu;
-    for (int e = tid; e < nE; e += blockDim.x) {
-      const int r = e / NC, c = e % NC;
-      double qq = 0.0;
-      for (int k = 0; k < 7; ++k) qq += sQ[r * 8 + k] * sQ[c * 8 + k];
-      sS[r * LD + c] = sS[r * LD + c] * ssc[r] * ssc[c] - qq * imu;
-    }
-    __syncthreads();
+    cov_cams_invert<7>(L, NC, NP, mu, Ag, T1, T2, bad);  // 6. - 8.
     if (ar.gauge == ACS_GAUGE_ANCHOR) {
       // 9. M <- P M P^T, P = I - K Cm, K = Q (Cm Q)^-1
       if (tid == 0) {
@@ -391,55 +267,20 @@ __global__ __launch_bounds__(256) void k_extcov_cams(ExtDims d, XcCamArgs ar, co
     if (anchored && (r / 6 == ar.a || c / 6 == ar.a)) v = 0.0;
     cov[e] = degenerate ? nan : v;
   }
-  // the report: sd extremes and the point sums, fixed-order trees
-  double rs = 0.0, ts = 0.0, sw = 0.0;
-  long long cnt[3] = {0, 0, 0}, m = 0;
-  for (int r = tid; r < NC; r += blockDim.x) {
-    double v = ar.s2 * sS[r * LD + r];
-    if (anchored && r / 6 == ar.a) v = 0.0;
-    const double sd = sqrt(v);
-    if (r % 6 < 3)
-      rs = fmax(rs, sd);
-    else
-      ts = fmax(ts, sd);
-  }
-  for (int i = tid; i < d.n; i += blockDim.x) {
-    const int s = status[i];
-    if (s >= 0 && s < 3) cnt[s]++;
-    sw += wr2[i];
-    m += nres[i];
-  }
-  __syncthreads();
-  double* rd = tmp;                         // 256 x 2: sum w r^2 and the rotation sd maximum
-  long long* ri = (long long*)(s_sm + 128);  // 256 x 4
-  rd[tid] = sw;
-  rd[256 + tid] = rs;
-  s_red[tid] = ts;
-  for (int k = 0; k < 3; ++k) ri[tid * 4 + k] = cnt[k];
-  ri[tid * 4 + 3] = m;
-  __syncthreads();
-  for (int h = 128; h > 0; h >>= 1) {
-    if (tid < h) {
-      rd[tid] += rd[tid + h];
-      rd[256 + tid] = fmax(rd[256 + tid], rd[256 + tid + h]);
-      s_red[tid] = fmax(s_red[tid], s_red[tid + h]);
-      for (int k = 0; k < 4; ++k) ri[tid * 4 + k] += ri[(tid + h) * 4 + k];
-    }
-    __syncthreads();
-  }
+  const CovCamsTotals tot = cov_cams_totals(L, NC, NP, ar.s2, anchored ? ar.a : -1, false, d.n, status, wr2, nres);
   if (tid == 0) {
-    const long long n_ok = ri[0], dof = ri[3] - 3 * n_ok - (6 * d.C - 7);
+    const long long n_ok = tot.n_ok, dof = tot.n_res - 3 * n_ok - (6 * d.C - 7);
     rep->status = degenerate ? ACS_EXT_COV_DEGENERATE : ACS_EXT_COV_OK;
     rep->reserved = 0;
     rep->n_points = d.n;
     rep->n_ok = n_ok;
-    rep->n_noobs = ri[1];
-    rep->n_degenerate = ri[2];
+    rep->n_noobs = tot.n_noobs;
+    rep->n_degenerate = tot.n_degenerate;
     rep->dof = dof;
     rep->min_pivot = gbad ? 0.0 : minp;
-    rep->sigma_hat_px = dof > 0 ? sqrt(rd[0] / (double)dof) : nan;
-    rep->rot_sd_max = degenerate ? nan : rd[256];
-    rep->trans_sd_max = degenerate ? nan : s_red[0];
+    rep->sigma_hat_px = dof > 0 ? sqrt(tot.wr2 / (double)dof) : nan;
+    rep->rot_sd_max = degenerate ? nan : tot.rot_sd_max;
+    rep->trans_sd_max = degenerate ? nan : tot.trans_sd_max;
   }
 }
 
@@ -621,7 +462,7 @@ int acs_sba_extrinsics_covariance(acs_ctx* ctx, const double* cams, int32_t n_ca
                      part);
   XcCamArgs ar{nchunk, anchored ? ACS_GAUGE_ANCHOR : ACS_GAUGE_FREE, anchored ? op.anchor_cam : 0,
                anchored ? op.scale_cam : 0, op.sigma_px * op.sigma_px};
-  hipLaunchKernelGGL(k_extcov_cams, dim3(1), dim3(256), extcov_cams_lds(NP), s, d, ar, part, in.cams, dst, wr2, nres, Ag,
+  hipLaunchKernelGGL(k_extcov_cams, dim3(1), dim3(256), cov_cams_lds(NP), s, d, ar, part, in.cams, dst, wr2, nres, Ag,
                      T1, T2, dcc, drep, bad);
   if (dcp) {
 #define XC_PTS(g)                                                                                                   \
